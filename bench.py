@@ -22,6 +22,10 @@ process with the same steps/warmup, each with its own roofline object.
 
 --workload c3 / c4 make one of those the line's headline instead (profiling aid); the default (c2) is the judged one.
 
+--dump-outputs DIR writes what the headline's last timed step computed to DIR/*.npy (a fixed sample, dump_outputs()), so that
+two builds given the same arguments can be compared output for output (N > 1: rank 0's shard); the line's "outputs_dumped"
+lists the files.
+
 Exit codes: 0 = the line was printed; 2 = refused (fewer GPUs than asked for); 3 = N > 1 only: the headline was measured and
 printed, but the gather-inclusive sample hung past --allgather-timeout and was abandoned (its "allgather" object says so).
 `roofline.launch_ms` = {min, median, max} of the timed launches (frac is computed from the median); `roofline.traffic` is
@@ -63,9 +67,15 @@ def parse(argv=None):
     ap.add_argument("--allgather-log2-chunk", type=int, default=12, help="N>1: witnesses per rank per gathered chunk")
     ap.add_argument("--allgather-timeout", type=float, default=240.0, help="N>1: seconds before the gather-inclusive sample is abandoned")
     ap.add_argument("--allgather-chunks", type=int, default=8, help="N>1: chunks in the gather-inclusive sample (0: skip)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (float64, a fixed "
+                         "sample of at most 64 MB: dump_outputs())")
     ap.add_argument("--n1-value", type=float, default=0.0, help="N>1: the N = 1 run's `value` (constraints/s), for the two efficiency figures "
                                                                  "of the line (absent: this run's own rank-0 rate stands in for it)")
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---- N > 1 without a launcher: start the ranks ourselves -------------------------------------------------------
@@ -671,6 +681,65 @@ def next_rows_of_single_calls(eng, dev, calls: int):
             "materialize": {"ms": m_ms, "rows_per_s": n / (m_ms / 1e3)}, "permutation": {"ms": p_ms, "rows_per_s": n / (p_ms / 1e3)}}
 
 
+# ---- --dump-outputs: what the headline's last step handed its caller ------------------------------------------
+
+DUMP_SAMPLE = 1 << 16   # entries sampled per array (all of them when the step has no more)
+DUMP_SEED = 0xD0        # the sample's positions: the same in every run with the same arguments
+DUMP_LIMIT = 64 << 20   # bytes, all files together
+
+
+def u64_words(a):
+    """int64 storage of u64 words (Montgomery limbs, Variable indices) -> float64, every word as its low and its high 32 bits
+    (exact): shape (n,) -> (n, 2), (n, k) -> (n, 2k)"""
+    import numpy as np
+    u = np.ascontiguousarray(a).view(np.uint64)
+    w = np.stack([u & np.uint64(0xFFFFFFFF), u >> np.uint64(32)], axis=-1).astype(np.float64)
+    return w.reshape(u.shape[0], -1) if u.ndim == 2 else w
+
+
+def dump_outputs(wl: Workload, out_dir: str) -> dict:
+    """the arrays the last timed step of `wl` handed its caller -- the nine columns and the result variables (c2_values: the
+    variable table) -- as out_dir/<name>.npy in u64_words() form.  A step of the default headline writes 233 GB: each array is
+    a fixed sample of DUMP_SAMPLE positions over the whole step, drawn with DUMP_SEED (out_dir/<row|var|item>_index.npy: the
+    positions); the inputs are seeded too, so the same arguments give the same files.  The launches of a step write the same
+    arrays one after the other: the last launch is sampled as the timed step left it, the earlier ones are launched once more
+    (same inputs, same arrays) and sampled in turn."""
+    import numpy as np
+    import torch
+    import plonk_gadgets_amd as pg
+    if isinstance(wl.cols, torch.Tensor):
+        arrays = {"var_values": ("var", wl.cols)}
+    else:
+        arrays = {n: ("row", getattr(wl.cols, n)) for n in pg.Columns.SCALAR_COLS + pg.Columns.WIRE_COLS}
+        arrays["var_values"] = ("var", wl.cols.var_values)
+    if wl.res is not None:
+        arrays["result_vars"] = ("item", wl.res)
+    rng = np.random.default_rng(DUMP_SEED)
+    picks = {}
+    for name, (kind, t) in arrays.items():
+        if kind not in picks:
+            total = t.shape[0] * wl.n_chunks
+            picks[kind] = np.arange(total) if total <= DUMP_SAMPLE else np.sort(rng.choice(total, DUMP_SAMPLE, replace=False))
+    parts = {name: {} for name in arrays}
+    last = wl.n_chunks - 1
+    for c in [last] + list(range(last)):
+        if c != last:
+            wl.launch(c)
+        torch.cuda.synchronize(wl.dev)
+        for name, (kind, t) in arrays.items():
+            n, pos = t.shape[0], picks[kind]
+            local = pos[(pos >= c * n) & (pos < (c + 1) * n)] - c * n
+            parts[name][c] = t.index_select(0, torch.from_numpy(local).to(wl.dev)).cpu().numpy()
+    files = {name: u64_words(np.concatenate([got[c] for c in range(wl.n_chunks)])) for name, got in parts.items()}
+    files.update({kind + "_index": pos.astype(np.float64) for kind, pos in picks.items()})
+    size = sum(a.nbytes for a in files.values())
+    assert size <= DUMP_LIMIT, size
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(n + ".npy" for n in files), "bytes": size, "sample": DUMP_SAMPLE, "seed": DUMP_SEED}
+
+
 def kernel_sources_sha256() -> str:
     """what the library is built from (plonk_gadgets_amd.build.kernel_sources_sha256): the PMC passes under profiles/ say
     which sources they were collected for"""
@@ -837,6 +906,8 @@ def main():
         el_s, ms_s = measure(wl, args.steps, warm, sync_all)
         steady = {"warmup": warm, "warmup_note": "180 ms of work, as long as five steps of the default headline (c2)",
                   "ms_per_step": el_s / args.steps * 1e3, "value": constraints / el_s, "frac": roofline_of(wl, ms_s)["frac"]}
+    # (before the bare-fill launches, which write over the workload's arrays)
+    dumped = dump_outputs(wl, args.dump_outputs) if args.dump_outputs and rank == 0 else None
     roofline = roofline_with_fill(wl, kernel_ms) if world == 1 and not args.no_fill else roofline_of(wl, kernel_ms)
     config = {"workload": wl.desc, "items_per_gpu": wl.batch, "items_per_launch": wl.chunk,
               "launches_per_step": wl.n_chunks,
@@ -919,6 +990,8 @@ def main():
     }
     if hbm_budget:
         line["hbm_budget"] = hbm_budget
+    if dumped:
+        line["outputs_dumped"] = dumped
     if secondary:
         line["secondary"] = secondary
 
