@@ -507,6 +507,28 @@ pg_status pg_composer_permutation_reserve(pg_composer *c, uint64_t sparse_positi
 pg_status pg_check_rows(pg_engine *e, const pg_columns *cols, uint64_t n_gates, uint64_t var_base, uint64_t n_vars,
                         pg_variable zero_var, int64_t *first_bad, void *stream);
 
+/* ---- the copy permutation as field elements: sigma evaluations and PLONK's grand product z ------------------------------
+ * dusk-plonk 0.8's Permutation::compute_permutation_lagrange and compute_(fast_)permutation_poly, in evaluation form, over the
+ * domain of padded_n = 2^m rows.  Engine-level calls over caller arrays (from pg_composer_materialize / _permutation or
+ * anywhere else).  Conventions [DEP-RECALL] (the Python layer's defaults; arguments here):
+ *   k = (1, K1, K2, K3) = (1, 7, 13, 17), one coset constant per wire, in sigma's wire order (left, right, output, fourth);
+ *   omega = ROOT_OF_UNITY^(2^(32 - m)), ROOT_OF_UNITY = 7^t with q - 1 = 2^32 t (pg_domain_generator).
+ * Host: the generator of the 2^log2_n subgroup (log2_n <= 32), Montgomery form. */
+pg_status pg_domain_generator(uint32_t log2_n, pg_scalar *out);
+/* d_out[4 * padded_n] = k[s / padded_n] * omega^(s mod padded_n) for s = d_sigma[p] (padded_n a power of two <= 2^32).  An
+ * entry s >= 4 * padded_n -> PG_ERR_INVALID_ARGUMENT (found on the device; nothing is read out of bounds).  Synchronises. */
+pg_status pg_sigma_evaluations(pg_engine *e, const uint64_t *d_sigma, uint64_t padded_n, const pg_scalar *omega, const pg_scalar k[4],
+                               pg_scalar *d_out, void *stream);
+/* The copy permutation's grand product: with num_i = prod_j (w_j[i] + beta k_j omega^i + gamma) and
+ * den_i = prod_j (w_j[i] + beta sigma_eval_j[i] + gamma), j = 0..3, d_z[i] = prod_{r < i} num_r / den_r for i < padded_n
+ * (d_z[0] = 1) and *d_wrap (one device scalar) = the product of all padded_n ratios: one iff (with overwhelming probability
+ * over beta, gamma) the wire values are constant on sigma's cycles.  d_wire_values[j] (device) hold n_values <= padded_n
+ * entries; rows >= n_values read as zero (the prover pads the witness with zeros).  A zero denominator ->
+ * PG_ERR_NON_EXISTING_INVERSE; bad sizes or sigma entries -> PG_ERR_INVALID_ARGUMENT.  Synchronises `stream`. */
+pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scalar *const d_wire_values[4], uint64_t n_values,
+                                 const uint64_t *d_sigma, const pg_scalar *omega, const pg_scalar k[4], const pg_scalar *beta,
+                                 const pg_scalar *gamma, pg_scalar *d_z, pg_scalar *d_wrap, void *stream);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

@@ -13,15 +13,21 @@ Every call appends on the GPU through the C ABI (pg_composer_*, pg_range_check, 
 from __future__ import annotations
 
 import ctypes as C
+import hashlib
 from dataclasses import dataclass
 
 import torch
 
 from . import _lib
 from .engine import Columns, Engine, NonExistingInverse, PgError
-from .scalar import BlsScalar
+from .scalar import Q, BlsScalar
 
 Variable = int
+
+
+def _label_scalar(label: str) -> BlsScalar:
+    """a fixed, non-trivial field element: SHA-256 of the label, reduced mod q"""
+    return BlsScalar.from_int(int.from_bytes(hashlib.sha256(label.encode()).digest(), "little") % Q)
 
 
 def _chk(st: int, where: str):
@@ -365,6 +371,26 @@ class StandardComposer:
         _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
         return t
 
+    def wire_values(self) -> list:
+        """the four wire-VALUE columns of materialize() (w_l, w_r, w_o, w_4 values: int64[circuit_size, 4] each), nothing else"""
+        n, dev = self.circuit_size(), self.engine.device
+        vals = [torch.empty((n, 4), dtype=torch.int64, device=dev) for _ in range(4)]
+        fc = _lib.FullColumnsC(w_l_value=vals[0].data_ptr(), w_r_value=vals[1].data_ptr(), w_o_value=vals[2].data_ptr(),
+                               w_4_value=vals[3].data_ptr())
+        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        return vals
+
+    def copy_constraints_hold(self, beta=None, gamma=None, padded_n: int | None = None) -> bool:
+        """the copy-constraint counterpart of check(): the wire values are constant on the cycles of the copy permutation
+        (permutation(padded_n)) iff PLONK's grand product over the padded domain wraps to one -- for all but a negligible share
+        of (beta, gamma), which default to fixed hashes.  padded_n defaults to the next power of two >= circuit_size."""
+        padded_n = padded_n or 1 << max(0, (self.circuit_size() - 1).bit_length())
+        vals = self.wire_values()
+        sigma = self.permutation(padded_n)
+        beta = _label_scalar("plonk_gadgets_amd copy constraints beta") if beta is None else beta
+        gamma = _label_scalar("plonk_gadgets_amd copy constraints gamma") if gamma is None else gamma
+        _, wrap = self.engine.permutation_product(vals, sigma, beta, gamma)
+        return wrap.to_int() == 1
 
 @dataclass
 class AllocatedScalar:

@@ -25,6 +25,7 @@
 #include "composer.hpp"
 #include "permutation.hpp"
 #include "materialize.hpp"
+#include "permutation_product.hpp"
 
 #ifndef PG_GRID_BLOCKS_PER_CU
 // more workgroups than can be resident: the dispatcher back-fills CUs as tiles finish (+6 % over a persistent
@@ -127,6 +128,9 @@ struct pg_engine {
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     hipEvent_t ev_switch = nullptr;
+    // scratch of pg_sigma_evaluations / pg_permutation_product (grow-only): flags, omega tables, tile products, denominators
+    uint4 *d_pp = nullptr;
+    uint64_t pp_units = 0;  // (16-byte units)
 };
 
 namespace {
@@ -568,6 +572,7 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->d_err_count) (void)hipFree(e->d_err_count);
     if (e->d_blk_agg) (void)hipFree(e->d_blk_agg);
     if (e->d_prefix) (void)hipFree(e->d_prefix);
+    if (e->d_pp) (void)hipFree(e->d_pp);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
@@ -1144,6 +1149,153 @@ pg_status pg_fill_columns(pg_engine *e, const pg_columns *out, uint64_t n_gates,
                        static_cast<hipStream_t>(stream), O, n_gates, n_vars, rows_per_tile, vars_per_tile, pattern);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
+}
+
+}  // extern "C"
+
+/* ---- the copy permutation as field elements (permutation_product.hpp) ------------------------------------------------- */
+namespace {
+
+// ROOT_OF_UNITY = 7^t, q - 1 = 2^32 t: canonical limbs (order exactly 2^32)
+const uint64_t kRootOfUnity[4] = {0x3829971f439f0d2bull, 0xb63683508c2280b9ull, 0xd09b681922c813b4ull, 0x16a2a19edfe81f20ull};
+
+pg::Fr domain_generator(uint32_t log2_n) {
+    pg::Fr w = pg::fr_to_mont(pg::Fr{{kRootOfUnity[0], kRootOfUnity[1], kRootOfUnity[2], kRootOfUnity[3]}});
+    for (uint32_t i = log2_n; i < 32; i++) w = pg::fr_mul(w, w);
+    return w;
+}
+
+pg_status check_field(const pg_scalar *s, const char *what) {
+    if (!s) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " is NULL");
+    if (!is_reduced(to_fr(s))) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " is not reduced below the modulus");
+    return PG_OK;
+}
+
+// the call's domain: padded_n a power of two <= 2^32; scratch laid out as flags (1 unit) | lo | hi | the product's own arrays
+// (`extra` units); the tables built with multipliers c[j] on `st`
+pg_status pp_prepare(pg_engine *e, uint64_t padded_n, const pg_scalar *omega, const pg::Fr c[4], uint64_t extra, hipStream_t st,
+                     pg::PpDomain &D, uint32_t *&flags, uint4 *&rest) {
+    if (padded_n == 0 || (padded_n & (padded_n - 1)) || padded_n > (1ull << 32))
+        return fail(PG_ERR_INVALID_ARGUMENT, "padded_n must be a power of two <= 2^32");
+    PG_TRY(check_field(omega, "omega"));
+    D.padded_n = padded_n;
+    D.m = 0;
+    while ((1ull << D.m) < padded_n) D.m++;
+    D.L = D.m < pg::kPpLoBitsMax ? D.m : pg::kPpLoBitsMax;
+    D.H = padded_n >> D.L;
+    const uint64_t units = 1 + 2 * ((1ull << D.L) + 4 * D.H) + extra;
+    if (units > e->pp_units) {
+        if (e->d_pp) (void)hipFree(e->d_pp);
+        e->d_pp = nullptr;
+        e->pp_units = 0;
+        PG_HIP_TRY(hipMalloc(&e->d_pp, units * sizeof(uint4)));
+        e->pp_units = units;
+    }
+    flags = reinterpret_cast<uint32_t *>(e->d_pp);
+    uint4 *lo = e->d_pp + 1, *hi = lo + 2 * (1ull << D.L);
+    D.lo = lo;
+    D.hi = hi;
+    rest = hi + 8 * D.H;
+    pg::PpPowers P;
+    P.pw[0] = to_fr(omega);
+    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    for (int j = 0; j < 4; j++) P.c[j] = c[j];
+    PG_HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t), st));
+    const uint64_t entries = (1ull << D.L) + D.H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * 8;
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, D.L, D.H, lo, hi);
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
+}
+
+// the flags after the call's launches (synchronises)
+pg_status pp_finish(pg_engine *e, uint32_t *flags, hipStream_t st) {
+    uint32_t h = 0;
+    PG_HIP_TRY(hipGetLastError());
+    PG_HIP_TRY(hipMemcpyAsync(&h, flags, sizeof h, hipMemcpyDeviceToHost, st));
+    PG_HIP_TRY(hipStreamSynchronize(st));
+    (void)e;
+    if (h & pg::kPpFlagBadSigma) return fail(PG_ERR_INVALID_ARGUMENT, "a sigma entry is >= 4 * padded_n");
+    if (h & pg::kPpFlagZeroDen) return fail(PG_ERR_NON_EXISTING_INVERSE, "a denominator w + beta * sigma + gamma is zero");
+    return PG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+pg_status pg_domain_generator(uint32_t log2_n, pg_scalar *out) {
+    if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (log2_n > 32) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n > 32: the scalar field has no such subgroup");
+    from_fr(domain_generator(log2_n), out);
+    return PG_OK;
+}
+
+pg_status pg_sigma_evaluations(pg_engine *e, const uint64_t *d_sigma, uint64_t padded_n, const pg_scalar *omega, const pg_scalar k[4],
+                               pg_scalar *d_out, void *stream) {
+    if (!e || !k) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    PG_TRY(check_u64s(d_sigma, "d_sigma"));
+    PG_TRY(check_scalars(d_out, "d_out"));
+    pg::Fr c[4];
+    for (int j = 0; j < 4; j++) {
+        PG_TRY(check_field(&k[j], "k[j]"));
+        c[j] = to_fr(&k[j]);
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
+    pg::PpDomain D;
+    uint32_t *flags;
+    uint4 *rest;
+    PG_TRY(pp_prepare(e, padded_n, omega, c, 0, st, D, flags, rest));
+    const uint64_t want = (4 * padded_n + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * 32;
+    hipLaunchKernelGGL(pg::pp_sigma_eval_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, D, d_sigma,
+                       reinterpret_cast<uint4 *>(d_out), flags);
+    return pp_finish(e, flags, st);
+}
+
+pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scalar *const d_wire_values[4], uint64_t n_values,
+                                 const uint64_t *d_sigma, const pg_scalar *omega, const pg_scalar k[4], const pg_scalar *beta,
+                                 const pg_scalar *gamma, pg_scalar *d_z, pg_scalar *d_wrap, void *stream) {
+    if (!e || !k || (n_values && !d_wire_values)) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (n_values > padded_n) return fail(PG_ERR_INVALID_ARGUMENT, "n_values > padded_n");
+    PG_TRY(check_u64s(d_sigma, "d_sigma"));
+    PG_TRY(check_scalars(d_z, "d_z"));
+    PG_TRY(check_scalars(d_wrap, "d_wrap"));
+    PG_TRY(check_field(beta, "beta"));
+    PG_TRY(check_field(gamma, "gamma"));
+    pg::PpProduct A{};
+    for (int j = 0; j < 4 && n_values; j++) {
+        PG_TRY(check_scalars(d_wire_values[j], "d_wire_values[j]"));
+        A.w[j] = reinterpret_cast<const uint4 *>(d_wire_values[j]);
+    }
+    pg::Fr c[4];
+    for (int j = 0; j < 4; j++) {
+        PG_TRY(check_field(&k[j], "k[j]"));
+        c[j] = pg::fr_mul(to_fr(beta), to_fr(&k[j]));
+    }
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
+    const uint64_t tiles = (padded_n + pg::kPpTile - 1) / pg::kPpTile;
+    // launch 1 loops over the tiles with the workgroups that fit at once (two per CU: 178 registers), each owning a slab of denominators
+    const uint64_t resident = (uint64_t)e->num_cus * 2, grid = tiles < resident ? tiles : resident;
+    uint32_t *flags;
+    uint4 *rest;
+    PG_TRY(pp_prepare(e, padded_n, omega, c, 4 * tiles + 2 * grid * pg::kPpTile, st, A.D, flags, rest));
+    A.n_values = n_values;
+    A.sigma = d_sigma;
+    A.gamma = to_fr(gamma);
+    A.z = reinterpret_cast<uint4 *>(d_z);
+    A.wrap = reinterpret_cast<uint4 *>(d_wrap);
+    A.tile_prod = rest;
+    A.tile_carry = rest + 2 * tiles;
+    A.den = rest + 4 * tiles;
+    A.tiles = tiles;
+    A.flags = flags;
+    hipLaunchKernelGGL(pg::pp_ratio_kernel, dim3((uint32_t)grid), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::pp_carry_kernel, dim3(1), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::pp_scan_kernel, dim3((uint32_t)tiles), dim3(pg::kThreads), 0, st, A);
+    return pp_finish(e, flags, st);
 }
 
 }  // extern "C"

@@ -11,6 +11,23 @@ from . import _lib
 from .scalar import BlsScalar
 
 
+# [DEP-RECALL] dusk-plonk 0.8's coset constants (1, K1, K2, K3), one per wire in sigma's order (left, right, output, fourth)
+DEFAULT_K = (1, 7, 13, 17)
+
+
+def domain_generator(log2_n: int) -> BlsScalar:
+    """omega of the 2^log2_n subgroup (log2_n <= 32): ROOT_OF_UNITY^(2^(32 - log2_n)), ROOT_OF_UNITY = 7^((q - 1) / 2^32)"""
+    out = _lib.Scalar()
+    st = _lib.load().pg_domain_generator(log2_n, C.byref(out))
+    if st != 0:
+        raise PgError(st, "pg_domain_generator")
+    return BlsScalar(out)
+
+
+def _field(x) -> BlsScalar:
+    return x if isinstance(x, BlsScalar) else BlsScalar.from_int(int(x))
+
+
 class PgError(RuntimeError):
     def __init__(self, status: int, where: str):
         lib = _lib.load()
@@ -416,6 +433,48 @@ class Engine:
         if st != 0:
             raise PgError(st, "pg_check_rows")
         return bad.value
+
+    # ---- the copy permutation as field elements -------------------------------------------------------------
+    def _domain(self, sigma: torch.Tensor, omega, k):
+        assert sigma.is_cuda and sigma.dtype == torch.int64 and sigma.dim() == 2 and sigma.shape[0] == 4 and sigma.is_contiguous()
+        padded_n = sigma.shape[1]
+        if omega is None:
+            assert padded_n > 0 and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two"
+            omega = domain_generator(padded_n.bit_length() - 1)
+        ks = (_lib.Scalar * 4)(*[_field(x).c for x in k])
+        return padded_n, _field(omega), ks
+
+    def sigma_evaluations(self, sigma: torch.Tensor, omega=None, k=DEFAULT_K) -> torch.Tensor:
+        """sigma (int64[4, padded_n], StandardComposer.permutation) -> its evaluations k[wire] * omega^gate as int64[4, padded_n, 4]
+        (dusk-plonk's compute_permutation_lagrange); omega defaults to the generator of the padded_n subgroup"""
+        padded_n, om, ks = self._domain(sigma, omega, k)
+        out = torch.empty((4, padded_n, 4), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_sigma_evaluations(self._h, sigma.data_ptr(), padded_n, C.byref(om.c), ks, out.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_sigma_evaluations")
+        return out
+
+    def permutation_product(self, wire_values, sigma: torch.Tensor, beta, gamma, omega=None, k=DEFAULT_K):
+        """PLONK's copy-permutation grand product -> (z int64[padded_n, 4], wrap BlsScalar): z[i] = prod_{r < i} num_r / den_r,
+        wrap = the product of all padded_n ratios (one iff the wire values are constant on sigma's cycles).  wire_values: four
+        int64[n_values, 4] tensors (the w_l / w_r / w_o / w_4 values of StandardComposer.materialize), rows >= n_values read as 0.
+        Raises NonExistingInverse when a denominator is zero."""
+        padded_n, om, ks = self._domain(sigma, omega, k)
+        assert len(wire_values) == 4
+        n_values = wire_values[0].shape[0]
+        for w in wire_values:
+            self._check_scalars(w, n_values)
+        ptrs = (C.c_void_p * 4)(*[w.data_ptr() for w in wire_values])
+        z = torch.empty((padded_n, 4), dtype=torch.int64, device=self.device)
+        wrap = torch.empty((1, 4), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_permutation_product(self._h, padded_n, ptrs, n_values, sigma.data_ptr(), C.byref(om.c), ks,
+                                              C.byref(_field(beta).c), C.byref(_field(gamma).c), z.data_ptr(), wrap.data_ptr(),
+                                              self._stream())
+        if st == 1:
+            raise NonExistingInverse(st, "pg_permutation_product")
+        if st != 0:
+            raise PgError(st, "pg_permutation_product")
+        return z, BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in wrap[0].tolist()])
 
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
