@@ -5,7 +5,7 @@ A step = one pass of the hot path over one batch: 2^20 witnesses x (allocate + r
 ladder length n = 255, 1031 gate rows + 1034 variables per witness, emitted into the 8 live composer columns +
 the variable table, inputs already resident in HBM.  With N GPUs every rank processes its own 2^20 witnesses
 (weak scaling, contiguous witness shards emitted at their global numbering, no data-path collective in the timed
-region: SURVEY.md section 8e / DESIGN.md "Multi-GPU"); the gather-inclusive rate of the chunked all-gather
+region: SURVEY.md section 8e / DESIGN.md "Multi-GPU"); with --full, the gather-inclusive rate of the chunked all-gather
 pipeline is measured afterwards on a bounded sample and reported beside it ("allgather").
 
 `--gpus N` is honoured however the script is started:
@@ -15,10 +15,14 @@ pipeline is measured afterwards on a bounded sample and reported beside it ("all
     fewer than N GPUs is refused loudly -- the script never silently runs fewer ranks than it was asked for.
 
 Prints ONE JSON line (rank 0).  `roofline` is measured live with HIP events around every launch of the dominant
-kernel on the stream it runs on; `cpu_baseline` times the CPU oracle ("port" of the reference algorithm, one
-thread) on a bounded sample of the same workload on this box's host cores.  At N = 1 the line also carries
-`secondary`: BASELINE configs C3 (fused scalar mix) and C4 (max_bound, random 253-bit bounds) timed in the same
-process with the same steps/warmup, each with its own roofline object.
+kernel on the stream it runs on.  A plain run stops there: set-up, warm-up, the timed steps, --dump-outputs, the line.
+
+--full adds everything else the benchmark measures, each in runs of its own after the headline: `roofline.bare_fill`
+(the same-process store ceiling); `cpu_baseline`, which times the CPU oracle ("port" of the reference algorithm, one
+thread) on a bounded sample of the same workload on this box's host cores; at N = 1 `secondary`: BASELINE configs C3
+(fused scalar mix), C4 (max_bound, random 253-bit bounds), the C2 witness refresh and the f-rows, timed in the same
+process with the same steps/warmup, each with its own roofline object; at N > 1 `allgather`, the gather-inclusive
+sample.  --no-cpu / --no-secondary / --no-fill leave single parts of it out.
 
 --workload c3 / c4 make one of those the line's headline instead (profiling aid); the default (c2) is the judged one.
 
@@ -26,8 +30,9 @@ process with the same steps/warmup, each with its own roofline object.
 two builds given the same arguments can be compared output for output (N > 1: rank 0's shard); the line's "outputs_dumped"
 lists the files.
 
-Exit codes: 0 = the line was printed; 2 = refused (fewer GPUs than asked for); 3 = N > 1 only: the headline was measured and
-printed, but the gather-inclusive sample hung past --allgather-timeout and was abandoned (its "allgather" object says so).
+Exit codes: 0 = the line was printed; 2 = refused (fewer GPUs than asked for); 3 = N > 1 with --full only: the headline was
+measured and printed, but the gather-inclusive sample hung past --allgather-timeout and was abandoned (its "allgather" object
+says so).
 `roofline.launch_ms` = {min, median, max} of the timed launches (frac is computed from the median); `roofline.traffic` is
 null, with the reason in `traffic_source`, when profiles/pmc_summary.json was collected for other kernel sources.
 """
@@ -60,13 +65,16 @@ def parse(argv=None):
     ap.add_argument("--workload", choices=["c2", "c3", "c4", "c2_values"], default="c2")
     ap.add_argument("--log2-batch", type=int, default=20, help="items per GPU per step = 2^this")
     ap.add_argument("--log2-chunk", type=int, default=-1, help="items per launch = 2^this (-1: largest that fits)")
-    ap.add_argument("--cpu-sample", type=int, default=0, help="items timed on the CPU oracle (0: workload default)")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the C3 / C4 measurements after the headline")
-    ap.add_argument("--no-fill", action="store_true", help="skip the bare-fill comparison launches (profiling runs: only the workload's kernels)")
-    ap.add_argument("--allgather-log2-chunk", type=int, default=12, help="N>1: witnesses per rank per gathered chunk")
-    ap.add_argument("--allgather-timeout", type=float, default=240.0, help="N>1: seconds before the gather-inclusive sample is abandoned")
-    ap.add_argument("--allgather-chunks", type=int, default=8, help="N>1: chunks in the gather-inclusive sample (0: skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, measure everything else too: the bare-fill ceiling, the CPU baseline, at N = 1 the "
+                         "secondary workloads, at N > 1 the gather-inclusive sample (without it: the headline alone)")
+    ap.add_argument("--cpu-sample", type=int, default=0, help="--full: items timed on the CPU oracle (0: workload default)")
+    ap.add_argument("--no-cpu", action="store_true", help="--full: skip the CPU baseline")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the C3 / C4 measurements after the headline")
+    ap.add_argument("--no-fill", action="store_true", help="--full: skip the bare-fill comparison launches (profiling runs: only the workload's kernels)")
+    ap.add_argument("--allgather-log2-chunk", type=int, default=12, help="N>1, --full: witnesses per rank per gathered chunk")
+    ap.add_argument("--allgather-timeout", type=float, default=240.0, help="N>1, --full: seconds before the gather-inclusive sample is abandoned")
+    ap.add_argument("--allgather-chunks", type=int, default=8, help="N>1, --full: chunks in the gather-inclusive sample (0: skip)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the headline's last step computed to DIR/<name>.npy (float64, a fixed "
                          "sample of at most 64 MB: dump_outputs())")
@@ -75,6 +83,9 @@ def parse(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1:
         ap.error("--steps must be at least 1")
+    if not args.full:  # a plain run is the headline alone: every measurement after it is off
+        args.no_cpu = args.no_secondary = args.no_fill = True
+        args.allgather_chunks = 0
     return args
 
 

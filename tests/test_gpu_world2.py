@@ -141,7 +141,7 @@ def test_bench_five_ranks_rehearsal_with_the_gather_leg():
     gather-inclusive figures -- GatherPipeline (every packed chunk gathered) and VariablesOnlyPipeline (tables gathered, the other
     ranks' rows regenerated) -- with the watchdog armed and cancelled."""
     world, lg = 5, 8
-    p, lines = _run_bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--log2-batch", str(lg), "--no-cpu", "--allgather-log2-chunk", "5",
+    p, lines = _run_bench(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--log2-batch", str(lg), "--full", "--no-cpu", "--allgather-log2-chunk", "5",
                            "--allgather-chunks", "3", "--allgather-timeout", "240", "--n1-value", "1e9"], {"FAKE_RCCL_PIECE_BYTES": str(1 << 20)})
     assert p.returncode == 0, (p.returncode, p.stdout[-2000:], p.stderr[-4000:])
     assert len(lines) == 1, p.stdout
@@ -168,7 +168,7 @@ def test_bench_watchdog_abandons_a_gather_that_hangs():
     """a collective that does not come back (here: the stand-in publishes every exchange 3 s late, the limit is 2 s) must not
     cost the headline: rank 0 prints the line it has -- exactly one -- with the reason in `allgather.error`, and the run exits
     3, not 0; no rank is re-exec'd or restarted"""
-    p, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "8", "--no-cpu", "--allgather-log2-chunk", "5",
+    p, lines = _run_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--log2-batch", "8", "--full", "--no-cpu", "--allgather-log2-chunk", "5",
                            "--allgather-chunks", "2", "--allgather-timeout", "2"], {"FAKE_RCCL_DELAY_US": "3000000"}, timeout=300)
     assert p.returncode == 3, (p.returncode, p.stderr[-3000:])
     assert len(lines) == 1, p.stdout
@@ -178,7 +178,7 @@ def test_bench_watchdog_abandons_a_gather_that_hangs():
 def test_bench_refuses_a_gather_pipeline_that_cannot_fit():
     """the per-rank budget is checked before anything is allocated: two slots x (world + 1) packed chunks of 2^22 witnesses are
     5.6 TB -- refused with the figures, exit code non-zero, no line"""
-    p, lines = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--log2-batch", "8", "--no-cpu", "--allgather-log2-chunk", "22"], {},
+    p, lines = _run_bench(["--gpus", "2", "--steps", "1", "--warmup", "0", "--log2-batch", "8", "--full", "--no-cpu", "--allgather-log2-chunk", "22"], {},
                           timeout=300)
     assert p.returncode != 0 and not lines
     assert "gather pipeline alone needs" in p.stderr and "--allgather-log2-chunk" in p.stderr

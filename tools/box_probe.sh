@@ -9,7 +9,7 @@ OUT=gpurun_out/box_$T
 mkdir -p $OUT
 (rocm-smi --showcomputepartition --showmemorypartition --showclocks --showpower --showmaxpower --showfwinfo --showperflevel 2>&1 | head -120) > $OUT/rocm_smi.txt
 (rocminfo 2>&1 | grep -E "Name:|Compute Unit|Max Clock|Cache|Marketing|Uuid|Memory Properties|Size" | head -80) > $OUT/rocminfo.txt
-python3 bench.py --steps 10 --warmup 2 --no-cpu > $OUT/bench.json 2> $OUT/bench.err
+python3 bench.py --steps 10 --warmup 2 --full --no-cpu > $OUT/bench.json 2> $OUT/bench.err
 python3 tools/ab_emit.py run_c4 19 6 > $OUT/ab_c4.txt 2>/dev/null
 python3 tools/ab_emit.py run_c3 20 8 > $OUT/ab_c3.txt 2>/dev/null
 python3 - <<PY
