@@ -529,6 +529,24 @@ pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scala
                                  const uint64_t *d_sigma, const pg_scalar *omega, const pg_scalar k[4], const pg_scalar *beta,
                                  const pg_scalar *gamma, pg_scalar *d_z, pg_scalar *d_wrap, void *stream);
 
+/* ---- NTTs over the scalar field: interpolation and evaluation of the composer's columns -----------------------------------
+ * dusk-plonk 0.8's EvaluationDomain::{fft, ifft, coset_fft, coset_ifft} [DEP-RECALL] on n = 2^log2_n points (log2_n <= 32), in
+ * place on n_cols columns of d_data (device, Montgomery form): column j is d_data[j * col_stride .. j * col_stride + n),
+ * col_stride >= n.  Natural order in and out, outputs fully reduced:
+ *   PG_NTT_FORWARD:        e_j = sum_i c_i omega^(ij)
+ *   PG_NTT_INVERSE:        c_i = n^-1 sum_j e_j omega^(-ij)
+ *   PG_NTT_COSET_FORWARD:  the forward transform of c_i g^i
+ *   PG_NTT_COSET_INVERSE:  its exact inverse: the inverse transform, then times g^-i
+ * omega: a primitive 2^log2_n-th root of unity (omega^(2^(log2_n - 1)) = -1; omega = 1 for log2_n = 0), e.g. pg_domain_generator;
+ * coset_gen (g): nonzero, read only by the coset kinds (NULL otherwise; the Python layer's default is 7 [DEP-RECALL]).  The host
+ * checks them and computes n^-1, omega^-1 and g^-1 itself.  Bad sizes, a stride below n, a NULL or misaligned pointer, an omega
+ * of the wrong order or a zero g -> PG_ERR_INVALID_ARGUMENT with nothing launched.  Nothing on the device can fail, so the call
+ * only enqueues on `stream` and does not synchronise.  Device memory the engine keeps for it (grow-only):
+ * (2^L + n / 2^L) x 32 bytes, L = min(log2_n, 10), twice that for the coset kinds (64 MiB / 128 MiB at n = 2^31). */
+enum { PG_NTT_FORWARD = 0, PG_NTT_INVERSE = 1, PG_NTT_COSET_FORWARD = 2, PG_NTT_COSET_INVERSE = 3 };
+pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_stride, uint32_t log2_n, uint32_t kind,
+                 const pg_scalar *omega, const pg_scalar *coset_gen, void *stream);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

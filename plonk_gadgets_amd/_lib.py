@@ -183,6 +183,7 @@ SIGNATURES = {
     "pg_sigma_evaluations": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p]),
     "pg_permutation_product": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_void_p), C.c_uint64, C.c_void_p, _P(Scalar), _P(Scalar),
                                          _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_ntt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P(Scalar), _P(Scalar), C.c_void_p]),
     "pg_shard_range": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64)]),
     "pg_range_check_shard_layout": (C.c_int, [_P(Scalar), _P(Scalar), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                               _P(ShardC)]),

@@ -392,6 +392,44 @@ class StandardComposer:
         _, wrap = self.engine.permutation_product(vals, sigma, beta, gamma)
         return wrap.to_int() == 1
 
+    def _padded_n(self, padded_n: int | None) -> int:
+        return padded_n or 1 << max(0, (self.circuit_size() - 1).bit_length())
+
+    def wire_polynomials(self, padded_n: int | None = None) -> torch.Tensor:
+        """the four wire polynomials (w_l, w_r, w_o, w_4) as int64[4, padded_n, 4] coefficients: the wire values zero-padded to
+        the domain and interpolated in one call (the prover's round 1 without its blinding).  padded_n: a power of two >=
+        circuit_size, by default the next one."""
+        n, padded_n = self.circuit_size(), self._padded_n(padded_n)
+        assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
+        x = torch.zeros((4, padded_n, 4), dtype=torch.int64, device=self.engine.device)
+        fc = _lib.FullColumnsC(w_l_value=x[0].data_ptr(), w_r_value=x[1].data_ptr(), w_o_value=x[2].data_ptr(), w_4_value=x[3].data_ptr())
+        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        return self.engine.ifft(x, inplace=True)
+
+    def sigma_polynomials(self, padded_n: int | None = None) -> torch.Tensor:
+        """the four sigma polynomials as int64[4, padded_n, 4] coefficients: the ifft of sigma_evaluations(permutation(padded_n))
+        (dusk-plonk's compute_sigma_polynomials)"""
+        sigma = self.permutation(self._padded_n(padded_n))
+        return self.engine.ifft(self.engine.sigma_evaluations(sigma), inplace=True)
+
+    SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
+
+    def selector_polynomials(self, padded_n: int | None = None) -> dict:
+        """the eleven selector polynomials (SELECTORS: q_m .. q_c from device_columns(), the others from materialize()) as
+        int64[padded_n, 4] coefficients, interpolated in one call: with sigma_polynomials, the polynomial half of preprocess"""
+        n, padded_n = self.circuit_size(), self._padded_n(padded_n)
+        assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
+        x = torch.zeros((len(self.SELECTORS), padded_n, 4), dtype=torch.int64, device=self.engine.device)
+        cols = self.device_columns()
+        self.sync()
+        for i, name in enumerate(Columns.SCALAR_COLS):
+            x[i, :n] = getattr(cols, name)
+        del cols
+        fc = _lib.FullColumnsC(**{name: x[i].data_ptr() for i, name in enumerate(self.SELECTORS) if i >= len(Columns.SCALAR_COLS)})
+        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self.engine.ifft(x, inplace=True)
+        return {name: x[i] for i, name in enumerate(self.SELECTORS)}
+
 @dataclass
 class AllocatedScalar:
     """/root/reference/src/allocated_scalar.rs:17-30"""

@@ -26,6 +26,7 @@
 #include "permutation.hpp"
 #include "materialize.hpp"
 #include "permutation_product.hpp"
+#include "ntt.hpp"
 
 #ifndef PG_GRID_BLOCKS_PER_CU
 // more workgroups than can be resident: the dispatcher back-fills CUs as tiles finish (+6 % over a persistent
@@ -131,6 +132,9 @@ struct pg_engine {
     // scratch of pg_sigma_evaluations / pg_permutation_product (grow-only): flags, omega tables, tile products, denominators
     uint4 *d_pp = nullptr;
     uint64_t pp_units = 0;  // (16-byte units)
+    // scratch of pg_ntt (grow-only): its omega and coset tables
+    uint4 *d_ntt = nullptr;
+    uint64_t ntt_units = 0;  // (16-byte units)
 };
 
 namespace {
@@ -573,6 +577,7 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->d_blk_agg) (void)hipFree(e->d_blk_agg);
     if (e->d_prefix) (void)hipFree(e->d_prefix);
     if (e->d_pp) (void)hipFree(e->d_pp);
+    if (e->d_ntt) (void)hipFree(e->d_ntt);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
@@ -1202,7 +1207,7 @@ pg_status pp_prepare(pg_engine *e, uint64_t padded_n, const pg_scalar *omega, co
     for (int j = 0; j < 4; j++) P.c[j] = c[j];
     PG_HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t), st));
     const uint64_t entries = (1ull << D.L) + D.H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * 8;
-    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, D.L, D.H, lo, hi);
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, D.L, D.H, 4u, lo, hi);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }
@@ -1296,6 +1301,111 @@ pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scala
     hipLaunchKernelGGL(pg::pp_carry_kernel, dim3(1), dim3(pg::kThreads), 0, st, A);
     hipLaunchKernelGGL(pg::pp_scan_kernel, dim3((uint32_t)tiles), dim3(pg::kThreads), 0, st, A);
     return pp_finish(e, flags, st);
+}
+
+}  // extern "C"
+
+/* ---- NTTs over the scalar field (ntt.hpp) -------------------------------------------------------------------------------- */
+namespace {
+
+// the tables of base^x, x < 2^m, at `at` (2 (2^L + H) units), built on `st`: lo[e] = base^e, hi[h] = c base^(h 2^L)
+pg::NttTable ntt_table(const pg::Fr &base, const pg::Fr &c, uint32_t m, uint4 *at, int num_cus, hipStream_t st) {
+    const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
+    const uint64_t H = (1ull << m) >> L;
+    pg::PpPowers P{};
+    P.pw[0] = base;
+    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    P.c[0] = c;
+    const uint64_t entries = (1ull << L) + H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)num_cus * 8;
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, L, H, 1u, at,
+                       at + 2 * (1ull << L));
+    return pg::NttTable{at, at + 2 * (1ull << L), L};
+}
+
+}  // namespace
+
+extern "C" {
+
+pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_stride, uint32_t log2_n, uint32_t kind,
+                 const pg_scalar *omega, const pg_scalar *coset_gen, void *stream) {
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    PG_TRY(check_scalars(d_data, "d_data"));
+    if (log2_n > 32) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n > 32: the scalar field has no such subgroup");
+    if (kind > PG_NTT_COSET_INVERSE) return fail(PG_ERR_INVALID_ARGUMENT, "unknown kind");
+    const uint32_t m = log2_n;
+    const uint64_t n = 1ull << m;
+    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
+    if (n_cols && (n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
+        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    PG_TRY(check_field(omega, "omega"));
+    pg::Fr w = to_fr(omega), x = w;
+    for (uint32_t i = 1; i < m; i++) x = pg::fr_mul(x, x);
+    if (!pg::fr_eq(x, m ? pg::fr_neg_one() : pg::fr_one()))
+        return fail(PG_ERR_INVALID_ARGUMENT, "omega is not a primitive 2^log2_n-th root of unity");
+    const bool coset = kind == PG_NTT_COSET_FORWARD || kind == PG_NTT_COSET_INVERSE;
+    const bool inverse = kind == PG_NTT_INVERSE || kind == PG_NTT_COSET_INVERSE;
+    pg::Fr g = pg::fr_one();
+    if (coset) {
+        PG_TRY(check_field(coset_gen, "coset_gen"));
+        g = to_fr(coset_gen);
+        if (pg::fr_is_zero(g)) return fail(PG_ERR_INVALID_ARGUMENT, "coset_gen is zero");
+    }
+    if (n_cols == 0) return PG_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
+    const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
+    const uint64_t per_table = 2 * ((1ull << L) + (n >> L)), units = per_table * (coset ? 2 : 1);
+    if (units > e->ntt_units) {
+        if (e->d_ntt) (void)hipFree(e->d_ntt);
+        e->d_ntt = nullptr;
+        e->ntt_units = 0;
+        PG_HIP_TRY(hipMalloc(&e->d_ntt, units * sizeof(uint4)));
+        e->ntt_units = units;
+    }
+    const pg::Fr n_inv = pg::fr_invert_or_zero(pg::fr_from_u64(n));  // (n = 2^32 fits: fr_from_u64 takes the full 64 bits)
+    pg::NttPass P{};
+    P.data = reinterpret_cast<uint4 *>(d_data);
+    P.n_cols = n_cols;
+    P.stride = col_stride;
+    P.m = m;
+    P.w = ntt_table(inverse ? pg::fr_invert_or_zero(w) : w, pg::fr_one(), m, e->d_ntt, e->num_cus, st);
+    pg::NttTable none{nullptr, nullptr, 0}, gt = none;
+    if (coset) gt = inverse ? ntt_table(pg::fr_invert_or_zero(g), n_inv, m, e->d_ntt + per_table, e->num_cus, st)
+                            : ntt_table(g, pg::fr_one(), m, e->d_ntt + per_table, e->num_cus, st);
+    P.scale = n_inv;
+    P.use_scale = kind == PG_NTT_INVERSE;
+    const uint64_t resident = (uint64_t)e->num_cus * 3;  // (48 KiB of LDS per pass workgroup: three per CU)
+    auto pass = [&](uint32_t bp, uint32_t k, uint32_t cb, bool first, bool last) {
+        P.bp = bp;
+        P.k = k;
+        P.cb = cb;
+        P.twiddle = !last;
+        P.natural = m <= pg::kNttTileBits;
+        P.pre = first && coset && !inverse ? gt : none;
+        P.post = P.natural && coset && inverse ? gt : none;
+        const uint64_t tiles = n_cols << (m - k - cb);
+        hipLaunchKernelGGL(pg::ntt_pass_kernel, dim3((uint32_t)(tiles < resident ? tiles : resident)), dim3(pg::kThreads), 0, st, P);
+    };
+    if (m <= pg::kNttTileBits) {
+        pass(m, m, 0, true, true);
+    } else {
+        // the top m - 10 bits in passes of at most 2^7 points per column, as even as possible; then the last 2^10
+        const uint32_t top = m - pg::kNttTileBits, np = (top + pg::kNttStridedBits - 1) / pg::kNttStridedBits;
+        uint32_t bp = m;
+        for (uint32_t p = 0; p < np; p++) {
+            const uint32_t k = top / np + (p < top % np ? 1 : 0);
+            pass(bp, k, pg::kNttTileBits - k, p == 0, false);
+            bp -= k;
+        }
+        pass(bp, pg::kNttTileBits, 0, false, true);
+        P.pre = none;
+        P.post = coset && inverse ? gt : none;
+        const uint64_t tiles = n_cols << (m - 2 * pg::kNttRevBits), cap = (uint64_t)e->num_cus * 2;  // (66 KiB of LDS: two per CU)
+        hipLaunchKernelGGL(pg::ntt_reverse_kernel, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(pg::kThreads), 0, st, P);
+    }
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
 }
 
 }  // extern "C"

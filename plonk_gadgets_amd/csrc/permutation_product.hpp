@@ -41,8 +41,9 @@ struct PpPowers {
     Fr c[4];
 };
 
-// lo[e] = omega^e for e < 2^L; hi[j * H + h] = c[j] * omega^(h 2^L) for h < H = padded_n >> L
-__global__ __launch_bounds__(kThreads) void pp_tables_kernel(const PpPowers P, uint32_t L, uint64_t H, uint4 *lo, uint4 *hi) {
+// lo[e] = omega^e for e < 2^L; hi[j * H + h] = c[j] * omega^(h 2^L) for h < H = padded_n >> L and j < nc (<= 4).  (pw[b] may be
+// the powers of any base: ntt.hpp builds its tables of omega^x and of the coset generator's g^x here too.)
+__global__ __launch_bounds__(kThreads) void pp_tables_kernel(const PpPowers P, uint32_t L, uint64_t H, uint32_t nc, uint4 *lo, uint4 *hi) {
     const uint64_t nlo = 1ull << L;
     for (uint64_t e = (uint64_t)blockIdx.x * kThreads + threadIdx.x; e < nlo + H; e += (uint64_t)gridDim.x * kThreads) {
         const bool low = e < nlo;
@@ -59,7 +60,8 @@ __global__ __launch_bounds__(kThreads) void pp_tables_kernel(const PpPowers P, u
             continue;
         }
 #pragma unroll
-        for (int j = 0; j < 4; j++) {
+        for (uint32_t j = 0; j < 4; j++) {
+            if (j >= nc) break;
             o.f = fr_mul(P.c[j], acc);
             hi[2 * (j * H + x)] = o.v[0];
             hi[2 * (j * H + x) + 1] = o.v[1];

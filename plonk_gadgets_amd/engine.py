@@ -13,6 +13,10 @@ from .scalar import BlsScalar
 
 # [DEP-RECALL] dusk-plonk 0.8's coset constants (1, K1, K2, K3), one per wire in sigma's order (left, right, output, fourth)
 DEFAULT_K = (1, 7, 13, 17)
+# [DEP-RECALL] dusk-bls12_381's GENERATOR: the coset generator g of dusk-plonk 0.8's EvaluationDomain::coset_fft / coset_ifft
+DEFAULT_COSET_GENERATOR = 7
+# pg_ntt's kinds (include/plonk_gadgets_hip.h)
+NTT_KINDS = {"fft": 0, "ifft": 1, "coset_fft": 2, "coset_ifft": 3}
 
 
 def domain_generator(log2_n: int) -> BlsScalar:
@@ -475,6 +479,53 @@ class Engine:
         if st != 0:
             raise PgError(st, "pg_permutation_product")
         return z, BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in wrap[0].tolist()])
+
+    # ---- NTTs over the scalar field -----------------------------------------------------------------------------
+    def _ntt(self, kind: str, x: torch.Tensor, log2_n, omega, g, inplace: bool) -> torch.Tensor:
+        """x: int64[rows, 4] or int64[c, rows, 4] on the device (Montgomery limbs), rows <= 2^log2_n (log2_n defaults to the
+        smallest that holds them).  Fewer rows are zero-padded into a new tensor; inplace=True transforms x itself (no padding
+        allowed then: the point is to avoid the copy of a large column)."""
+        assert x.is_cuda and x.dtype == torch.int64 and x.dim() in (2, 3) and x.shape[-1] == 4
+        rows = x.shape[-2]
+        if log2_n is None:
+            log2_n = max(0, (rows - 1).bit_length())
+        n = 1 << log2_n
+        if rows > n:
+            raise ValueError(f"{rows} rows do not fit a domain of 2^{log2_n} points")
+        if inplace:
+            if rows != n:
+                raise ValueError("inplace=True needs exactly 2^log2_n rows: padding makes a new tensor")
+            if x.stride(-1) != 1 or x.stride(-2) != 4 or (x.dim() == 3 and x.stride(0) % 4):
+                raise ValueError("inplace=True needs rows of 4 contiguous limbs")
+            y = x
+        else:
+            y = torch.zeros(x.shape[:-2] + (n, 4), dtype=torch.int64, device=self.device)
+            y[..., :rows, :] = x
+        cols = y.shape[0] if y.dim() == 3 else 1
+        stride = y.stride(0) // 4 if cols > 1 else n  # (pg_ntt rejects a stride below n: overlapping columns)
+        om = domain_generator(log2_n) if omega is None else _field(omega)
+        coset = kind.startswith("coset")
+        gp = C.byref(_field(g).c) if coset else None
+        st = self._lib.pg_ntt(self._h, y.data_ptr(), cols, stride, log2_n, NTT_KINDS[kind], C.byref(om.c), gp, self._stream())
+        if st != 0:
+            raise PgError(st, "pg_ntt")
+        return y
+
+    def fft(self, x: torch.Tensor, log2_n=None, omega=None, g=DEFAULT_COSET_GENERATOR, inplace=False) -> torch.Tensor:
+        """coefficients -> evaluations e_j = sum_i c_i omega^(ij) over the 2^log2_n subgroup (EvaluationDomain::fft); g is unused"""
+        return self._ntt("fft", x, log2_n, omega, g, inplace)
+
+    def ifft(self, x: torch.Tensor, log2_n=None, omega=None, g=DEFAULT_COSET_GENERATOR, inplace=False) -> torch.Tensor:
+        """evaluations -> coefficients c_i = n^-1 sum_j e_j omega^(-ij) (EvaluationDomain::ifft); g is unused"""
+        return self._ntt("ifft", x, log2_n, omega, g, inplace)
+
+    def coset_fft(self, x: torch.Tensor, log2_n=None, omega=None, g=DEFAULT_COSET_GENERATOR, inplace=False) -> torch.Tensor:
+        """coefficients -> evaluations over the coset g<omega>: fft(c_i g^i) (EvaluationDomain::coset_fft)"""
+        return self._ntt("coset_fft", x, log2_n, omega, g, inplace)
+
+    def coset_ifft(self, x: torch.Tensor, log2_n=None, omega=None, g=DEFAULT_COSET_GENERATOR, inplace=False) -> torch.Tensor:
+        """the exact inverse of coset_fft: ifft, then times g^-i (EvaluationDomain::coset_ifft)"""
+        return self._ntt("coset_ifft", x, log2_n, omega, g, inplace)
 
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
