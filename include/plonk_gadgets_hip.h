@@ -547,6 +547,39 @@ enum { PG_NTT_FORWARD = 0, PG_NTT_INVERSE = 1, PG_NTT_COSET_FORWARD = 2, PG_NTT_
 pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_stride, uint32_t log2_n, uint32_t kind,
                  const pg_scalar *omega, const pg_scalar *coset_gen, void *stream);
 
+/* ---- the quotient polynomial and evaluations at a point: the prover's rounds 3 and 4 ------------------------------------
+ * pg_quotient: dusk-plonk 0.8's quotient_poly::compute [DEP-RECALL] for the arithmetic gate, the public inputs and the copy
+ * permutation, on n = 2^log2_n (log2_n <= 30; the inputs of 2^28 are the most one MI355X holds).  Every
+ * input is a polynomial of n coefficients (device, Montgomery form), e.g. StandardComposer.prover_polynomials().  With
+ * omega = omega_4n^4 (the generator of H), k = (k0..k3) the wire coset constants and x on the coset coset_gen * <omega_4n>:
+ *   N(x) = q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c) + PI
+ *        + alpha [ (a + beta k0 x + gamma)(b + beta k1 x + gamma)(c + beta k2 x + gamma)(d + beta k3 x + gamma) z(x)
+ *                - (a + beta sigma1 + gamma)(b + beta sigma2 + gamma)(c + beta sigma3 + gamma)(d + beta sigma4 + gamma) z(omega x) ]
+ *        + alpha^2 (z(x) - 1) L1(x),     L1(x) = (x^n - 1) / (n (x - 1))
+ * d_t (4n scalars) gets the polynomial t of degree < 4n with t(x) = N(x) / (x^n - 1) on those 4n points, as t_lo | t_mid | t_hi |
+ * t_4th (n coefficients each).  For a satisfied circuit with n >= 2, t (X^n - 1) = N exactly and deg t <= 4n - 5: the top four
+ * coefficients of t_4th are zero.
+ * d_scratch: PG_QUOTIENT_SCRATCH_COLS x n scalars the call overwrites (64 GiB at 2^28).  Bad sizes, a NULL (pi aside) or
+ * misaligned pointer, an omega_4n whose order is not exactly 4n, coset_gen = 0 or coset_gen^(4n) = 1, a d_t or d_scratch that
+ * overlaps an input or each other -> PG_ERR_INVALID_ARGUMENT with nothing launched.  Nothing on the device can fail, so the call
+ * only enqueues on `stream`.  Device memory the engine keeps for it (grow-only): pg_ntt's tables for n, and one more table of
+ * (2^L + n / 2^L) x 32 bytes, L = min(log2_n, 10) (8 MiB at 2^28). */
+typedef struct pg_quotient_polys {
+    const pg_scalar *w[4], *z, *sigma[4];
+    const pg_scalar *q_m, *q_l, *q_r, *q_o, *q_4, *q_c, *q_arith;
+    const pg_scalar *pi; /* NULL: the zero polynomial */
+} pg_quotient_polys;     /* each: n coefficients, device, Montgomery form */
+enum { PG_QUOTIENT_SCRATCH_COLS = 8 };
+pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
+                      const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
+                      pg_scalar *d_t, pg_scalar *d_scratch, void *stream);
+/* pg_poly_evaluate: d_out[j] = sum_{i < n} c_j[i] point^i for the n_cols columns c_j = d_coeffs + j * col_stride (device,
+ * Montgomery form; 1 <= n <= 2^32, col_stride >= n; point^0 = 1, so point = 0 gives c_j[0]).  A bad n or stride, a NULL or
+ * misaligned pointer, or a point not reduced below the modulus -> PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise
+ * the call only enqueues.  Device memory the engine keeps for it (grow-only): (257 + (n_cols + 1) ceil(n / 16384)) x 32 bytes. */
+pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_cols, uint64_t col_stride, uint64_t n,
+                           const pg_scalar *point, pg_scalar *d_out, void *stream);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

@@ -51,6 +51,12 @@ class LayoutC(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("num_bits", "gates_per_item", "vars_per_item", "n_gates", "n_vars")]
 
 
+class QuotientPolysC(C.Structure):
+    """pg_quotient_polys: device pointers to the quotient's inputs (pi may be NULL)"""
+    _fields_ = [("w", C.c_void_p * 4), ("z", C.c_void_p), ("sigma", C.c_void_p * 4)] + [
+        (n, C.c_void_p) for n in ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "pi")]
+
+
 # every symbol include/plonk_gadgets_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -184,6 +190,9 @@ SIGNATURES = {
     "pg_permutation_product": (C.c_int, [C.c_void_p, C.c_uint64, _P(C.c_void_p), C.c_uint64, C.c_void_p, _P(Scalar), _P(Scalar),
                                          _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_ntt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P(Scalar), _P(Scalar), C.c_void_p]),
+    "pg_quotient": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar),
+                              _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_poly_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p]),
     "pg_shard_range": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64)]),
     "pg_range_check_shard_layout": (C.c_int, [_P(Scalar), _P(Scalar), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                               _P(ShardC)]),

@@ -10,7 +10,7 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplonk_gadgets_hip.so")
 SOURCES = ["capi.hip"]
 HEADERS = ["experiment.hpp", "fr.hpp", "emit.hpp", "invert.hpp", "range_gadgets.hpp", "scalar_gadgets.hpp", "composer.hpp", "permutation.hpp", "materialize.hpp",
-           "permutation_product.hpp", "ntt.hpp", "capi_composer.inc", "capi_dist.inc"]
+           "permutation_product.hpp", "ntt.hpp", "quotient.hpp", "capi_composer.inc", "capi_dist.inc"]
 
 
 def hipcc() -> str:

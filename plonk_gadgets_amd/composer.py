@@ -430,6 +430,64 @@ class StandardComposer:
         self.engine.ifft(x, inplace=True)
         return {name: x[i] for i, name in enumerate(self.SELECTORS)}
 
+    def permutation_polynomial(self, beta, gamma, padded_n: int | None = None) -> torch.Tensor:
+        """the grand product z as int64[padded_n, 4] coefficients: the ifft of permutation_product's z over permutation(padded_n)
+        (the prover's round 2 without its blinding).  Raises NonExistingInverse as the product does."""
+        padded_n = self._padded_n(padded_n)
+        z, _ = self.engine.permutation_product(self.wire_values(), self.permutation(padded_n), beta, gamma)
+        return self.engine.ifft(z, inplace=True)
+
+    def public_input_polynomial(self, padded_n: int | None = None) -> torch.Tensor:
+        """PI as int64[padded_n, 4] coefficients: the ifft of construct_dense_pi_vec() zero-padded to the domain"""
+        n, padded_n = self.circuit_size(), self._padded_n(padded_n)
+        assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
+        x = torch.zeros((padded_n, 4), dtype=torch.int64, device=self.engine.device)
+        x[:n] = self.construct_dense_pi_vec()
+        return self.engine.ifft(x, inplace=True)
+
+    NON_ARITHMETIC_SELECTORS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
+
+    def prover_polynomials(self, beta, gamma, padded_n: int | None = None) -> dict:
+        """the 17 inputs of Engine.quotient as coefficients over the padded domain, keyed by its arguments: wires
+        (int64[4, padded_n, 4]), z (permutation_polynomial), sigmas (sigma_polynomials), selectors (the seven of
+        Engine.QUOTIENT_SELECTORS) and pi (public_input_polynomial).  Nothing refers to the composer afterwards, so it may be
+        closed before the quotient is computed.  Raises ValueError if a selector of the widgets the quotient leaves out (range,
+        logic, fixed- and variable-base group additions) is not zero, and NonExistingInverse as the grand product does."""
+        n, padded_n = self.circuit_size(), self._padded_n(padded_n)
+        assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
+        dev = self.engine.device
+        buf = torch.empty((n, 4), dtype=torch.int64, device=dev)
+        for name in self.NON_ARITHMETIC_SELECTORS:
+            _chk(self._lib.pg_composer_materialize(self._h, C.byref(_lib.FullColumnsC(**{name: buf.data_ptr()}))), "materialize")
+            if bool(buf.any()):
+                raise ValueError(f"{name} is not zero: the quotient covers the arithmetic gate and the copy permutation only")
+        del buf
+        names = self.engine.QUOTIENT_SELECTORS
+        sel = torch.zeros((len(names), padded_n, 4), dtype=torch.int64, device=dev)
+        cols = self.device_columns()
+        self.sync()
+        for name in Columns.SCALAR_COLS:
+            sel[names.index(name), :n] = getattr(cols, name)
+        del cols
+        wires = torch.zeros((4, padded_n, 4), dtype=torch.int64, device=dev)
+        fc = _lib.FullColumnsC(q_4=sel[names.index("q_4")].data_ptr(), q_arith=sel[names.index("q_arith")].data_ptr(),
+                               **{f"w_{w}_value": wires[j].data_ptr() for j, w in enumerate("lro4")})
+        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self.engine.ifft(sel, inplace=True)
+        sigma = self.permutation(padded_n)
+        z, _ = self.engine.permutation_product([wires[j, :n] for j in range(4)], sigma, beta, gamma)
+        self.engine.ifft(z, inplace=True)
+        self.engine.ifft(wires, inplace=True)
+        sigmas = self.engine.sigma_evaluations(sigma)
+        del sigma
+        self.engine.ifft(sigmas, inplace=True)
+        return {"wires": wires, "z": z, "sigmas": sigmas, "selectors": {name: sel[i] for i, name in enumerate(names)},
+                "pi": self.public_input_polynomial(padded_n)}
+
+    def quotient_polynomial(self, alpha, beta, gamma, padded_n: int | None = None) -> torch.Tensor:
+        """the quotient polynomial t as int64[4, padded_n, 4] (t_lo, t_mid, t_hi, t_4th): Engine.quotient of prover_polynomials()"""
+        return self.engine.quotient(**self.prover_polynomials(beta, gamma, padded_n), alpha=alpha, beta=beta, gamma=gamma)
+
 @dataclass
 class AllocatedScalar:
     """/root/reference/src/allocated_scalar.rs:17-30"""

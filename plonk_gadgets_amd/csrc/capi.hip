@@ -27,6 +27,7 @@
 #include "materialize.hpp"
 #include "permutation_product.hpp"
 #include "ntt.hpp"
+#include "quotient.hpp"
 
 #ifndef PG_GRID_BLOCKS_PER_CU
 // more workgroups than can be resident: the dispatcher back-fills CUs as tiles finish (+6 % over a persistent
@@ -135,6 +136,9 @@ struct pg_engine {
     // scratch of pg_ntt (grow-only): its omega and coset tables
     uint4 *d_ntt = nullptr;
     uint64_t ntt_units = 0;  // (16-byte units)
+    // scratch of pg_quotient (grow-only): its table of the chunk's points x; of pg_poly_evaluate: its power tables and partial sums
+    uint4 *d_quot = nullptr, *d_eval = nullptr;
+    uint64_t quot_units = 0, eval_units = 0;  // (16-byte units)
 };
 
 namespace {
@@ -578,6 +582,8 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->d_prefix) (void)hipFree(e->d_prefix);
     if (e->d_pp) (void)hipFree(e->d_pp);
     if (e->d_ntt) (void)hipFree(e->d_ntt);
+    if (e->d_quot) (void)hipFree(e->d_quot);
+    if (e->d_eval) (void)hipFree(e->d_eval);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
@@ -1322,6 +1328,67 @@ pg::NttTable ntt_table(const pg::Fr &base, const pg::Fr &c, uint32_t m, uint4 *a
     return pg::NttTable{at, at + 2 * (1ull << L), L};
 }
 
+// enqueue the transform of pg_ntt (its arguments checked, `st` entered) on the n_cols columns of `data`; src non-NULL: the columns
+// are read from src (same stride) and written to data (out of place, in the first pass)
+pg_status ntt_enqueue(pg_engine *e, uint4 *data, const uint4 *src, uint64_t n_cols, uint64_t col_stride, uint32_t m, bool coset,
+                      bool inverse, const pg::Fr &w, const pg::Fr &g, hipStream_t st) {
+    const uint64_t n = 1ull << m;
+    const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
+    const uint64_t per_table = 2 * ((1ull << L) + (n >> L)), units = per_table * (coset ? 2 : 1);
+    if (units > e->ntt_units) {
+        if (e->d_ntt) (void)hipFree(e->d_ntt);
+        e->d_ntt = nullptr;
+        e->ntt_units = 0;
+        PG_HIP_TRY(hipMalloc(&e->d_ntt, units * sizeof(uint4)));
+        e->ntt_units = units;
+    }
+    const pg::Fr n_inv = pg::fr_invert_or_zero(pg::fr_from_u64(n));  // (n = 2^32 fits: fr_from_u64 takes the full 64 bits)
+    pg::NttPass P{};
+    P.data = data;
+    P.n_cols = n_cols;
+    P.stride = col_stride;
+    P.m = m;
+    P.w = ntt_table(inverse ? pg::fr_invert_or_zero(w) : w, pg::fr_one(), m, e->d_ntt, e->num_cus, st);
+    pg::NttTable none{nullptr, nullptr, 0}, gt = none;
+    if (coset) gt = inverse ? ntt_table(pg::fr_invert_or_zero(g), n_inv, m, e->d_ntt + per_table, e->num_cus, st)
+                            : ntt_table(g, pg::fr_one(), m, e->d_ntt + per_table, e->num_cus, st);
+    P.scale = n_inv;
+    P.use_scale = inverse && !coset;
+    const uint64_t resident = (uint64_t)e->num_cus * 3;  // (48 KiB of LDS per pass workgroup: three per CU)
+    auto pass = [&](uint32_t bp, uint32_t k, uint32_t cb, bool first, bool last) {
+        P.bp = bp;
+        P.k = k;
+        P.cb = cb;
+        P.twiddle = !last;
+        P.natural = m <= pg::kNttTileBits;
+        P.src = first ? src : nullptr;
+        P.pre = first && coset && !inverse ? gt : none;
+        P.post = P.natural && coset && inverse ? gt : none;
+        const uint64_t tiles = n_cols << (m - k - cb);
+        hipLaunchKernelGGL(pg::ntt_pass_kernel, dim3((uint32_t)(tiles < resident ? tiles : resident)), dim3(pg::kThreads), 0, st, P);
+    };
+    if (m <= pg::kNttTileBits) {
+        pass(m, m, 0, true, true);
+    } else {
+        // the top m - 10 bits in passes of at most 2^7 points per column, as even as possible; then the last 2^10
+        const uint32_t top = m - pg::kNttTileBits, np = (top + pg::kNttStridedBits - 1) / pg::kNttStridedBits;
+        uint32_t bp = m;
+        for (uint32_t p = 0; p < np; p++) {
+            const uint32_t k = top / np + (p < top % np ? 1 : 0);
+            pass(bp, k, pg::kNttTileBits - k, p == 0, false);
+            bp -= k;
+        }
+        pass(bp, pg::kNttTileBits, 0, false, true);
+        P.src = nullptr;
+        P.pre = none;
+        P.post = coset && inverse ? gt : none;
+        const uint64_t tiles = n_cols << (m - 2 * pg::kNttRevBits), cap = (uint64_t)e->num_cus * 2;  // (66 KiB of LDS: two per CU)
+        hipLaunchKernelGGL(pg::ntt_reverse_kernel, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(pg::kThreads), 0, st, P);
+    }
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -1354,56 +1421,182 @@ pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
+    return ntt_enqueue(e, reinterpret_cast<uint4 *>(d_data), nullptr, n_cols, col_stride, m, coset, inverse, w, g, st);
+}
+
+}  // extern "C"
+
+/* ---- the quotient polynomial and evaluations at a point (quotient.hpp) -------------------------------------------------- */
+namespace {
+
+// a grow-only engine buffer of at least `units` 16-byte units
+pg_status grow_units(uint4 *&buf, uint64_t &have, uint64_t units) {
+    if (units <= have) return PG_OK;
+    if (buf) (void)hipFree(buf);
+    buf = nullptr;
+    have = 0;
+    PG_HIP_TRY(hipMalloc(&buf, units * sizeof(uint4)));
+    have = units;
+    return PG_OK;
+}
+
+bool overlaps(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
+    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
+    return x < y + b_bytes && y < x + a_bytes;
+}
+
+pg::Fr fr_sqr_times(pg::Fr x, uint32_t times) {  // x^(2^times)
+    for (uint32_t i = 0; i < times; i++) x = pg::fr_mul(x, x);
+    return x;
+}
+
+// workgroups for `items` work items of kThreads lanes, at most per_cu per CU (the kernels loop over the rest)
+uint32_t grid_of(const pg_engine *e, uint64_t items, uint64_t per_cu) {
+    const uint64_t want = (items + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * per_cu;
+    return (uint32_t)(want < cap ? (want ? want : 1) : cap);
+}
+
+template <int OP>
+void quotient_step(const pg_engine *e, const pg::QuotientChunk &A, hipStream_t st) {
+    const uint32_t grid = OP == pg::QS_PERM_NUM ? grid_of(e, (A.n + pg::kQRowsPerLane - 1) / pg::kQRowsPerLane, 8) : grid_of(e, A.n, 8);
+    hipLaunchKernelGGL(pg::quotient_step_kernel<OP>, dim3(grid), dim3(pg::kThreads), 0, st, A);
+}
+
+}  // namespace
+
+extern "C" {
+
+pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
+                      const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
+                      pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
+    if (!e || !p || !k) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    if (log2_n > 30) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n > 30");
+    const uint32_t m = log2_n;
+    const uint64_t n = 1ull << m, col_bytes = n * sizeof(pg_scalar);
+    // the inputs in the order the chunks consume them; pi (the last) may be NULL
+    const pg_scalar *in[17] = {p->w[0], p->w[1], p->w[2], p->w[3], p->z, p->q_m, p->q_l, p->q_r, p->q_o, p->q_4,
+                               p->q_c, p->q_arith, p->sigma[0], p->sigma[1], p->sigma[2], p->sigma[3], p->pi};
+    for (int i = 0; i < 16; i++) PG_TRY(check_scalars(in[i], "an input polynomial"));
+    if (p->pi) PG_TRY(check_scalars(p->pi, "pi"));
+    PG_TRY(check_scalars(d_t, "d_t"));
+    PG_TRY(check_scalars(d_scratch, "d_scratch"));
+    PG_TRY(check_field(alpha, "alpha"));
+    PG_TRY(check_field(beta, "beta"));
+    PG_TRY(check_field(gamma, "gamma"));
+    PG_TRY(check_field(omega_4n, "omega_4n"));
+    PG_TRY(check_field(coset_gen, "coset_gen"));
+    for (int j = 0; j < 4; j++) PG_TRY(check_field(&k[j], "k[j]"));
+    const pg::Fr zeta = to_fr(omega_4n), g = to_fr(coset_gen);
+    if (!pg::fr_eq(fr_sqr_times(zeta, m + 1), pg::fr_neg_one()))
+        return fail(PG_ERR_INVALID_ARGUMENT, "omega_4n is not a primitive 4n-th root of unity");
+    if (pg::fr_is_zero(g) || pg::fr_eq(fr_sqr_times(g, m + 2), pg::fr_one()))
+        return fail(PG_ERR_INVALID_ARGUMENT, "coset_gen is zero or coset_gen^(4n) = 1: the coset meets H");
+    const uint64_t t_bytes = 4 * col_bytes, s_bytes = PG_QUOTIENT_SCRATCH_COLS * col_bytes;
+    if (overlaps(d_t, t_bytes, d_scratch, s_bytes)) return fail(PG_ERR_INVALID_ARGUMENT, "d_t overlaps d_scratch");
+    for (const pg_scalar *x : in)
+        if (x && (overlaps(d_t, t_bytes, x, col_bytes) || overlaps(d_scratch, s_bytes, x, col_bytes)))
+            return fail(PG_ERR_INVALID_ARGUMENT, "d_t or d_scratch overlaps an input polynomial");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
     const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
-    const uint64_t per_table = 2 * ((1ull << L) + (n >> L)), units = per_table * (coset ? 2 : 1);
-    if (units > e->ntt_units) {
-        if (e->d_ntt) (void)hipFree(e->d_ntt);
-        e->d_ntt = nullptr;
-        e->ntt_units = 0;
-        PG_HIP_TRY(hipMalloc(&e->d_ntt, units * sizeof(uint4)));
-        e->ntt_units = units;
+    PG_TRY(grow_units(e->d_quot, e->quot_units, 2 * ((1ull << L) + (n >> L))));
+    const pg::Fr omega = fr_sqr_times(zeta, 2), zeta_n = fr_sqr_times(zeta, m), g_n = fr_sqr_times(g, m);
+    uint4 *T = reinterpret_cast<uint4 *>(d_t), *S = reinterpret_cast<uint4 *>(d_scratch);
+    pg::QuotientChunk A{};
+    A.s = S;
+    A.n = n;
+    A.has_pi = p->pi != nullptr;
+    A.alpha = to_fr(alpha);
+    A.beta = to_fr(beta);
+    A.gamma = to_fr(gamma);
+    for (int j = 0; j < 4; j++) A.beta_k[j] = pg::fr_mul(A.beta, to_fr(&k[j]));
+    A.n_fr = pg::fr_from_u64(n);
+    const pg::Fr alpha2 = pg::fr_mul(A.alpha, A.alpha);
+    pg::Fr g_j = g, zeta_jn = pg::fr_one();  // g zeta^j, zeta^(jn)
+    for (uint32_t j = 0; j < 4; j++) {
+        // coset-forward transform of input i into scratch column c, with generator g_j
+        auto fwd = [&](int i, uint32_t c) {
+            return ntt_enqueue(e, S + 2 * c * n, reinterpret_cast<const uint4 *>(in[i]), 1, n, m, true, false, omega, g_j, st);
+        };
+        const pg::Fr c_j = pg::fr_sub(pg::fr_mul(g_n, zeta_jn), pg::fr_one());  // x^n - 1 on the chunk
+        A.t = T + 2 * j * n;
+        A.x = ntt_table(omega, g_j, m, e->d_quot, e->num_cus, st);
+        A.alpha2_c = pg::fr_mul(alpha2, c_j);
+        A.c_inv = pg::fr_invert_or_zero(c_j);
+        for (int i = 0; i < 5; i++) PG_TRY(fwd(i, (uint32_t)i));  // a, b, c, d, z: resident for the chunk
+        quotient_step<pg::QS_PERM_NUM>(e, A, st);
+        PG_TRY(fwd(5, 5)); PG_TRY(fwd(6, 6)); PG_TRY(fwd(7, 7));  // q_m, q_l, q_r
+        quotient_step<pg::QS_GATE1>(e, A, st);
+        PG_TRY(fwd(8, 6)); PG_TRY(fwd(9, 7));  // q_o, q_4
+        quotient_step<pg::QS_GATE2>(e, A, st);
+        PG_TRY(fwd(10, 6)); PG_TRY(fwd(11, 7));  // q_c, q_arith
+        quotient_step<pg::QS_GATE3>(e, A, st);
+        if (p->pi) PG_TRY(fwd(16, 5));
+        PG_TRY(fwd(12, 6)); PG_TRY(fwd(13, 7));  // sigma_1, sigma_2
+        quotient_step<pg::QS_PERM1>(e, A, st);
+        PG_TRY(fwd(14, 5)); PG_TRY(fwd(15, 7));  // sigma_3, sigma_4
+        quotient_step<pg::QS_PERM2>(e, A, st);
+        // chunk j of t, in place: sum_k1 t[k0 + n k1] g_j^(n k1)
+        PG_TRY(ntt_enqueue(e, A.t, nullptr, 1, n, m, true, true, omega, g_j, st));
+        g_j = pg::fr_mul(g_j, zeta);
+        zeta_jn = pg::fr_mul(zeta_jn, zeta_n);
     }
-    const pg::Fr n_inv = pg::fr_invert_or_zero(pg::fr_from_u64(n));  // (n = 2^32 fits: fr_from_u64 takes the full 64 bits)
-    pg::NttPass P{};
-    P.data = reinterpret_cast<uint4 *>(d_data);
-    P.n_cols = n_cols;
-    P.stride = col_stride;
-    P.m = m;
-    P.w = ntt_table(inverse ? pg::fr_invert_or_zero(w) : w, pg::fr_one(), m, e->d_ntt, e->num_cus, st);
-    pg::NttTable none{nullptr, nullptr, 0}, gt = none;
-    if (coset) gt = inverse ? ntt_table(pg::fr_invert_or_zero(g), n_inv, m, e->d_ntt + per_table, e->num_cus, st)
-                            : ntt_table(g, pg::fr_one(), m, e->d_ntt + per_table, e->num_cus, st);
-    P.scale = n_inv;
-    P.use_scale = kind == PG_NTT_INVERSE;
-    const uint64_t resident = (uint64_t)e->num_cus * 3;  // (48 KiB of LDS per pass workgroup: three per CU)
-    auto pass = [&](uint32_t bp, uint32_t k, uint32_t cb, bool first, bool last) {
-        P.bp = bp;
-        P.k = k;
-        P.cb = cb;
-        P.twiddle = !last;
-        P.natural = m <= pg::kNttTileBits;
-        P.pre = first && coset && !inverse ? gt : none;
-        P.post = P.natural && coset && inverse ? gt : none;
-        const uint64_t tiles = n_cols << (m - k - cb);
-        hipLaunchKernelGGL(pg::ntt_pass_kernel, dim3((uint32_t)(tiles < resident ? tiles : resident)), dim3(pg::kThreads), 0, st, P);
-    };
-    if (m <= pg::kNttTileBits) {
-        pass(m, m, 0, true, true);
-    } else {
-        // the top m - 10 bits in passes of at most 2^7 points per column, as even as possible; then the last 2^10
-        const uint32_t top = m - pg::kNttTileBits, np = (top + pg::kNttStridedBits - 1) / pg::kNttStridedBits;
-        uint32_t bp = m;
-        for (uint32_t p = 0; p < np; p++) {
-            const uint32_t k = top / np + (p < top % np ? 1 : 0);
-            pass(bp, k, pg::kNttTileBits - k, p == 0, false);
-            bp -= k;
-        }
-        pass(bp, pg::kNttTileBits, 0, false, true);
-        P.pre = none;
-        P.post = coset && inverse ? gt : none;
-        const uint64_t tiles = n_cols << (m - 2 * pg::kNttRevBits), cap = (uint64_t)e->num_cus * 2;  // (66 KiB of LDS: two per CU)
-        hipLaunchKernelGGL(pg::ntt_reverse_kernel, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(pg::kThreads), 0, st, P);
-    }
+    pg::QuotientCombine Cb{};
+    Cb.t = T;
+    Cb.n = n;
+    Cb.iota = pg::fr_invert_or_zero(zeta_n);
+    const pg::Fr g_n_inv = pg::fr_invert_or_zero(g_n);
+    Cb.scale[0] = pg::fr_invert_or_zero(pg::fr_from_u64(4));
+    for (int j = 1; j < 4; j++) Cb.scale[j] = pg::fr_mul(Cb.scale[j - 1], g_n_inv);
+    hipLaunchKernelGGL(pg::quotient_combine_kernel, dim3(grid_of(e, n, 8)), dim3(pg::kThreads), 0, st, Cb);
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
+}
+
+pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_cols, uint64_t col_stride, uint64_t n,
+                           const pg_scalar *point, pg_scalar *d_out, void *stream) {
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    PG_TRY(check_scalars(d_coeffs, "d_coeffs"));
+    PG_TRY(check_scalars(d_out, "d_out"));
+    PG_TRY(check_field(point, "point"));
+    if (n == 0 || n > (1ull << 32)) return fail(PG_ERR_INVALID_ARGUMENT, "n must be in [1, 2^32]");
+    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
+    if (n_cols && (n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
+        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    if (n_cols == 0) return PG_OK;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
+    pg::PolyEval A{};
+    A.segs = (n + pg::kEvalSeg - 1) / pg::kEvalSeg;
+    PG_TRY(grow_units(e->d_eval, e->eval_units, 2 * (257 + (n_cols + 1) * A.segs)));
+    uint4 *lane = e->d_eval, *seg_lo = lane + 2 * 256, *seg = seg_lo + 2;
+    A.c = reinterpret_cast<const uint4 *>(d_coeffs);
+    A.n_cols = n_cols;
+    A.stride = col_stride;
+    A.n = n;
+    A.x_lane = lane;
+    A.x_seg = seg;
+    A.partial = seg + 2 * A.segs;
+    A.out = reinterpret_cast<uint4 *>(d_out);
+    const pg::Fr x = to_fr(point);
+    A.x256 = fr_sqr_times(x, 8);
+    // lane[t] = x^t (t < 256); seg[s] = x^(s kEvalSeg) (s < segs)
+    pg::PpPowers P{};
+    P.pw[0] = x;
+    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    P.c[0] = pg::fr_one();
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(1), dim3(pg::kThreads), 0, st, P, 8u, (uint64_t)0, 1u, lane, lane);
+    P.pw[0] = fr_sqr_times(x, 14);
+    static_assert(pg::kEvalSeg == (1u << 14), "x^kEvalSeg");
+    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(grid_of(e, A.segs + 1, 8)), dim3(pg::kThreads), 0, st, P, 0u, A.segs, 1u, seg_lo, seg);
+    hipLaunchKernelGGL(pg::poly_eval_kernel, dim3((uint32_t)(n_cols * A.segs < (uint64_t)e->num_cus * 8 ? n_cols * A.segs
+                                                                                                         : (uint64_t)e->num_cus * 8)),
+                       dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::poly_eval_reduce_kernel, dim3((uint32_t)(n_cols < (uint64_t)e->num_cus * 8 ? n_cols : (uint64_t)e->num_cus * 8)),
+                       dim3(pg::kThreads), 0, st, A);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }

@@ -45,6 +45,7 @@ __device__ __forceinline__ uint32_t ntt_rev(uint32_t x, uint32_t bits) { return 
 
 struct NttPass {
     uint4 *data;              // column j at data + 2 * j * stride (points of 32 bytes)
+    const uint4 *src;         // non-NULL: the first pass reads its column j at src + 2 * j * stride instead (out of place)
     uint64_t n_cols, stride;
     uint32_t m, bp, k, cb;    // log2 of: n, the block, R (points per column of a tile), the adjacent columns per tile
     uint32_t twiddle;         // multiply output u of column c by omega^((n / N) c u): every pass but the last
@@ -79,9 +80,10 @@ __global__ __launch_bounds__(kThreads) void ntt_pass_kernel(const NttPass P) {
         const uint64_t first = ((r >> gbits) << P.bp) + ((r & ((1ull << gbits) - 1)) << cb);  // index of point (0, 0) in the column
         const uint64_t c0 = first & (S - 1);
         uint4 *base = P.data + 2 * (col * P.stride + first);
+        const uint4 *in = P.src ? P.src + 2 * (col * P.stride + first) : base;
         for (uint32_t e = threadIdx.x; e < T; e += kThreads) {
             const uint64_t off = (e & (C - 1)) + S * (e >> cb);
-            Fr x = pp_load(base, off);
+            Fr x = pp_load(in, off);
             if (P.pre.lo) x = fr_mul(x, ntt_pow(P.pre, first + off));
             tile[e].f = x;
         }

@@ -1,0 +1,213 @@
+// quotient.hpp -- the prover's round 3 and round 4 over the scalar field (gfx950): PLONK's quotient polynomial t(X) and the
+// evaluation of polynomials at a point.
+//
+// The quotient, with the conventions [DEP-RECALL] of dusk-plonk 0.8's quotient_poly::compute: n = 2^m
+// points of H = <omega>, zeta a primitive 4n-th root of unity with zeta^4 = omega, g the coset generator, k_0..k_3 the wires'
+// coset constants; every input a polynomial of n coefficients.  At x on the coset g<zeta> (4n points)
+//   N(x) = q_arith (q_m a b + q_l a + q_r b + q_o c + q_4 d + q_c) + PI
+//        + alpha [ prod_j (w_j + beta k_j x + gamma) z(x) - prod_j (w_j + beta sigma_j + gamma) z(omega x) ]
+//        + alpha^2 (z(x) - 1) L1(x),         L1(x) = (x^n - 1) / (n (x - 1))
+// and t is the polynomial of degree < 4n with t(x) = N(x) / (x^n - 1) on those points, returned as t_lo | t_mid | t_hi | t_4th.
+//
+// The 4n points are four cosets of H: chunk j (j < 4) holds x = g_j omega^i, g_j = g zeta^j, i < n.  So every transform is an
+// n-point one of ntt.hpp (a polynomial of degree < n needs no folding), z(omega x) is entry (i + 1) mod n of the same chunk, and
+// x^n - 1 = c_j = g^n zeta^(jn) - 1 is a constant of the chunk.  Per chunk, the host (capi.hip, pg_quotient) enqueues:
+//   * coset-forward transforms with g_j, out of place (the first pass reads the caller's coefficients), of a, b, c, d and z into
+//     scratch columns 0..4, which stay for the whole chunk; the selectors and sigmas stream through columns 5..7;
+//   * quotient_step_kernel<QS_*> launches that accumulate N / c_j into chunk j of d_t (the order below);
+//   * after the four chunks, a coset-inverse transform of each chunk with g_j, in place: coefficient k0 of chunk j is then
+//     r_j = sum_k1 t[k0 + n k1] g^(n k1) zeta^(j n k1), and quotient_combine_kernel inverts that 4-point DFT (root zeta^n) per k0
+//     and multiplies by 4^-1 g^(-n k1), in place.
+// x is ONE multiplication through pp_tables_kernel's two tables (lo[e] = omega^e, hi[h] = g_j omega^(h 2^L)).  The 1 / (n (x - 1))
+// of L1 comes from Montgomery's trick per lane over kQRowsPerLane points (as pp_ratio_kernel does): the running products go to
+// d_t and are read back by the same lane, and n (x - 1) is recomputed from the table instead of being stored.  x - 1 and c_j are
+// never zero once the host has checked g^(4n) != 1, so nothing on the device can fail.
+// No scratch memory, no LDS; 64-bit indices wherever one can reach 4n.
+//
+// The evaluation (pg_poly_evaluate): sum_{i < n} c_i x^i for n_cols columns at a stride, any n from 1 to 2^32.  A segment of
+// kEvalSeg points per workgroup step: lane t reads points s + 256 k + t (coalesced) and runs Horner along them (acc = acc x^256
+// + c: one multiplication per coefficient), multiplies by x^t (a 256-entry table) and the workgroup sums the lanes in LDS; lane 0
+// multiplies by x^s (a table over the segments) and writes the segment's partial sum.  poly_eval_reduce_kernel sums a column's
+// partials.
+#pragma once
+
+#include "ntt.hpp"
+
+namespace pg {
+
+constexpr uint32_t kQRowsPerLane = 32;                               // Montgomery's trick: one inversion per 32 points
+constexpr uint64_t kQTile = (uint64_t)kThreads * kQRowsPerLane;      // 8192 points
+constexpr uint32_t kEvalPerLane = 64;                                // Horner steps per lane and segment
+constexpr uint64_t kEvalSeg = (uint64_t)kThreads * kEvalPerLane;     // 16384 points per segment
+
+// the pointwise steps of one chunk, in launch order, and the scratch columns (s[0..7]) each reads
+enum : int {
+    QS_PERM_NUM = 0,  // t  = alpha z prod_j (w_j + beta k_j x + gamma) + alpha^2 c_j (z - 1) / (n (x - 1))    (s0..s4)
+    QS_GATE1 = 1,     // s5 = q_m a b + q_l a + q_r b                                   (s5 = q_m, s6 = q_l, s7 = q_r)
+    QS_GATE2 = 2,     // s5 += q_o c + q_4 d                                            (s6 = q_o, s7 = q_4)
+    QS_GATE3 = 3,     // t  += q_arith (s5 + q_c)                                       (s6 = q_c, s7 = q_arith)
+    QS_PERM1 = 4,     // t  += PI (if any);  s6 = (a + beta sigma_1 + gamma)(b + beta sigma_2 + gamma)   (s5 = PI, s6, s7 = sigma_1, _2)
+    QS_PERM2 = 5,     // t  = (t - alpha s6 (c + beta sigma_3 + gamma)(d + beta sigma_4 + gamma) z(omega x)) c_j^-1   (s5, s7 = sigma_3, _4)
+};
+
+struct QuotientChunk {
+    uint4 *t;             // chunk j of d_t: n points
+    uint4 *s;             // scratch: column c at s + 2 c n
+    uint64_t n;
+    uint32_t has_pi;
+    NttTable x;           // x = g_j omega^i
+    Fr alpha, beta, gamma;
+    Fr beta_k[4];         // beta k_j
+    Fr n_fr;              // n as a field element
+    Fr alpha2_c;          // alpha^2 c_j
+    Fr c_inv;             // c_j^-1
+};
+
+__device__ __forceinline__ Fr q_col(const QuotientChunk &A, uint32_t c, uint64_t i) { return pp_load(A.s, c * A.n + i); }
+
+// one of QS_GATE1 .. QS_PERM2 (see the enum) at point i
+template <int OP>
+__device__ __forceinline__ void quotient_point(const QuotientChunk &A, uint64_t i) {
+    if (OP == QS_GATE1) {
+        const Fr a = q_col(A, 0, i), b = q_col(A, 1, i);
+        const Fr ab = fr_mul(fr_add(fr_mul(q_col(A, 5, i), a), q_col(A, 7, i)), b);  // (q_m a + q_r) b
+        pp_store(A.s, 5 * A.n + i, fr_add(ab, fr_mul(q_col(A, 6, i), a)));
+    } else if (OP == QS_GATE2) {
+        const Fr g = fr_add(fr_mul(q_col(A, 6, i), q_col(A, 2, i)), fr_mul(q_col(A, 7, i), q_col(A, 3, i)));
+        pp_store(A.s, 5 * A.n + i, fr_add(q_col(A, 5, i), g));
+    } else if (OP == QS_GATE3) {
+        const Fr g = fr_mul(q_col(A, 7, i), fr_add(q_col(A, 5, i), q_col(A, 6, i)));
+        pp_store(A.t, i, fr_add(pp_load(A.t, i), g));
+    } else if (OP == QS_PERM1) {
+        if (A.has_pi) pp_store(A.t, i, fr_add(pp_load(A.t, i), q_col(A, 5, i)));
+        const Fr f0 = fr_add(fr_add(q_col(A, 0, i), fr_mul(A.beta, q_col(A, 6, i))), A.gamma);
+        const Fr f1 = fr_add(fr_add(q_col(A, 1, i), fr_mul(A.beta, q_col(A, 7, i))), A.gamma);
+        pp_store(A.s, 6 * A.n + i, fr_mul(f0, f1));
+    } else if (OP == QS_PERM2) {
+        const Fr f2 = fr_add(fr_add(q_col(A, 2, i), fr_mul(A.beta, q_col(A, 5, i))), A.gamma);
+        const Fr f3 = fr_add(fr_add(q_col(A, 3, i), fr_mul(A.beta, q_col(A, 7, i))), A.gamma);
+        const Fr zw = q_col(A, 4, (i + 1) & (A.n - 1));
+        const Fr den = fr_mul(fr_mul(fr_mul(q_col(A, 6, i), f2), fr_mul(f3, zw)), A.alpha);
+        pp_store(A.t, i, fr_mul(fr_sub(pp_load(A.t, i), den), A.c_inv));
+    }
+}
+
+template <int OP>
+__global__ __launch_bounds__(kThreads) void quotient_step_kernel(const QuotientChunk A) {
+    if (OP != QS_PERM_NUM) {
+        for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < A.n; i += (uint64_t)gridDim.x * kThreads)
+            quotient_point<OP>(A, i);
+        return;
+    }
+    // QS_PERM_NUM: a tile of kQTile points per workgroup step, lane t taking points t, t + 256, ... of it
+    const uint32_t t = threadIdx.x;
+    const uint64_t tiles = (A.n + kQTile - 1) / kQTile;
+#pragma unroll 1
+    for (uint64_t tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        const uint64_t base = tile * kQTile;
+        Fr P = fr_one();  // running product of d_k = n (x_k - 1)
+#pragma unroll 1
+        for (uint32_t k = 0; k < kQRowsPerLane; k++) {
+            const uint64_t i = base + (uint64_t)k * kThreads + t;
+            if (i >= A.n) break;
+            const Fr d = fr_sub(fr_mul(A.n_fr, ntt_pow(A.x, i)), A.n_fr);
+            pp_store(A.t, i, P);  // P_{k-1}
+            P = fr_mul(P, d);
+        }
+        Fr I = fr_invert_or_zero(P);  // 1 / P_last
+#pragma unroll 1
+        for (int k = (int)kQRowsPerLane - 1; k >= 0; k--) {
+            const uint64_t i = base + (uint64_t)k * kThreads + t;
+            if (i >= A.n) continue;
+            const Fr x = ntt_pow(A.x, i);
+            const Fr d = fr_sub(fr_mul(A.n_fr, x), A.n_fr);
+            const Fr inv = fr_mul(I, pp_load(A.t, i));  // 1 / d_k = P_{k-1} / P_k
+            I = fr_mul(I, d);                            // 1 / P_{k-1}
+            const Fr z = q_col(A, 4, i);
+            Fr num = z;
+#pragma unroll
+            for (uint32_t j = 0; j < 4; j++) num = fr_mul(num, fr_add(fr_add(q_col(A, j, i), fr_mul(A.beta_k[j], x)), A.gamma));
+            const Fr l1 = fr_mul(fr_mul(fr_sub(z, fr_one()), inv), A.alpha2_c);
+            pp_store(A.t, i, fr_add(fr_mul(num, A.alpha), l1));
+        }
+    }
+}
+
+// the inverse 4-point DFT across the chunks, per k0 < n, in place: r_j = t[j n + k0] -> t[k0 + n k1] = scale[k1] sum_j iota^(j k1) r_j,
+// iota = zeta^-n (iota^2 = -1), scale[k1] = 4^-1 g^(-n k1)
+struct QuotientCombine {
+    uint4 *t;
+    uint64_t n;
+    Fr iota;
+    Fr scale[4];
+};
+__global__ __launch_bounds__(kThreads) void quotient_combine_kernel(const QuotientCombine A) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < A.n; i += (uint64_t)gridDim.x * kThreads) {
+        const Fr r0 = pp_load(A.t, i), r1 = pp_load(A.t, A.n + i), r2 = pp_load(A.t, 2 * A.n + i), r3 = pp_load(A.t, 3 * A.n + i);
+        const Fr e0 = fr_add(r0, r2), e1 = fr_sub(r0, r2), o0 = fr_add(r1, r3), o1 = fr_mul(A.iota, fr_sub(r1, r3));
+        pp_store(A.t, i, fr_mul(fr_add(e0, o0), A.scale[0]));
+        pp_store(A.t, A.n + i, fr_mul(fr_add(e1, o1), A.scale[1]));
+        pp_store(A.t, 2 * A.n + i, fr_mul(fr_sub(e0, o0), A.scale[2]));
+        pp_store(A.t, 3 * A.n + i, fr_mul(fr_sub(e1, o1), A.scale[3]));
+    }
+}
+
+// ---- evaluation at a point ----------------------------------------------------------------------------------------------------
+struct PolyEval {
+    const uint4 *c;          // column j at c + 2 j stride
+    uint64_t n_cols, stride, n, segs;  // segs = ceil(n / kEvalSeg)
+    Fr x256;                 // x^256
+    const uint4 *x_lane;     // x^t, t < 256
+    const uint4 *x_seg;      // x^(s kEvalSeg), s < segs
+    uint4 *partial;          // n_cols x segs
+    uint4 *out;              // n_cols
+};
+
+// the sum of the 256 lanes' x (every lane calls it; lane 0 gets the sum); buf: 256 entries of LDS
+__device__ __forceinline__ Fr eval_block_sum(const Fr &x, FrVec *buf) {
+    const uint32_t t = threadIdx.x;
+    buf[t].f = x;
+    __syncthreads();
+#pragma unroll
+    for (uint32_t h = kThreads / 2; h > 0; h >>= 1) {
+        if (t < h) buf[t].f = fr_add(buf[t].f, buf[t + h].f);
+        __syncthreads();
+    }
+    const Fr r = buf[0].f;
+    __syncthreads();  // (buf is reused)
+    return r;
+}
+
+__global__ __launch_bounds__(kThreads) void poly_eval_kernel(const PolyEval A) {
+    __shared__ FrVec buf[kThreads];
+    const uint32_t t = threadIdx.x;
+    const Fr xt = pp_load(A.x_lane, t);
+    const uint64_t items = A.n_cols * A.segs;
+#pragma unroll 1
+    for (uint64_t it = blockIdx.x; it < items; it += gridDim.x) {
+        const uint64_t col = it / A.segs, seg = it - col * A.segs, first = seg * kEvalSeg;
+        const uint4 *c = A.c + 2 * col * A.stride;
+        Fr acc = fr_zero();
+#pragma unroll 4
+        for (int k = (int)kEvalPerLane - 1; k >= 0; k--) {
+            const uint64_t i = first + (uint64_t)k * kThreads + t;
+            acc = fr_add(fr_mul(acc, A.x256), i < A.n ? pp_load(c, i) : fr_zero());
+        }
+        const Fr sum = eval_block_sum(fr_mul(acc, xt), buf);
+        if (t == 0) pp_store(A.partial, it, fr_mul(sum, pp_load(A.x_seg, seg)));
+    }
+}
+
+// one column per workgroup step
+__global__ __launch_bounds__(kThreads) void poly_eval_reduce_kernel(const PolyEval A) {
+    __shared__ FrVec buf[kThreads];
+#pragma unroll 1
+    for (uint64_t col = blockIdx.x; col < A.n_cols; col += gridDim.x) {
+        Fr acc = fr_zero();
+        for (uint64_t s = threadIdx.x; s < A.segs; s += kThreads) acc = fr_add(acc, pp_load(A.partial, col * A.segs + s));
+        const Fr sum = eval_block_sum(acc, buf);
+        if (threadIdx.x == 0) pp_store(A.out, col, sum);
+    }
+}
+
+}  // namespace pg

@@ -527,6 +527,69 @@ class Engine:
         """the exact inverse of coset_fft: ifft, then times g^-i (EvaluationDomain::coset_ifft)"""
         return self._ntt("coset_ifft", x, log2_n, omega, g, inplace)
 
+    # ---- the quotient polynomial and evaluations at a point ---------------------------------------------------
+    QUOTIENT_SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith")
+
+    @staticmethod
+    def _rows(t: torch.Tensor) -> bool:
+        """rows of 4 contiguous limbs on the device"""
+        return t.is_cuda and t.dtype == torch.int64 and t.shape[-1] == 4 and t.stride(-1) == 1 and t.stride(-2) == 4
+
+    def quotient(self, wires, z, sigmas, selectors: dict, pi=None, *, alpha, beta, gamma, omega_4n=None, k=DEFAULT_K,
+                 g=DEFAULT_COSET_GENERATOR, scratch=None) -> torch.Tensor:
+        """PLONK's quotient polynomial t (pg_quotient, the prover's round 3 for the arithmetic gate, the public inputs and the copy
+        permutation) as int64[4, n, 4]: t_lo, t_mid, t_hi, t_4th.  Every input is a polynomial of n = 2^m coefficients
+        (int64[n, 4] on the device; wires and sigmas: four of them, or int64[4, n, 4]); selectors: QUOTIENT_SELECTORS -> tensor;
+        pi None is the zero polynomial.  omega_4n defaults to domain_generator(m + 2) (whose fourth power is the domain's omega);
+        scratch: int64[PG_QUOTIENT_SCRATCH_COLS = 8, n, 4] the call may overwrite (allocated if None).
+        StandardComposer.prover_polynomials() gives all of them."""
+        polys = [wires[j] for j in range(4)] + [z] + [sigmas[j] for j in range(4)] + [selectors[s] for s in self.QUOTIENT_SELECTORS]
+        n = polys[0].shape[0]
+        if n < 1 or n & (n - 1) or n > 1 << 30:
+            raise ValueError(f"n = {n} must be a power of two <= 2^30")
+        for t in polys + ([] if pi is None else [pi]):
+            if not (self._rows(t) and t.dim() == 2 and t.shape[0] == n):
+                raise ValueError(f"every input must be int64[{n}, 4] on the device with contiguous rows")
+        log2_n = n.bit_length() - 1
+        if scratch is None:
+            scratch = torch.empty((8, n, 4), dtype=torch.int64, device=self.device)
+        elif not (self._rows(scratch) and scratch.is_contiguous() and scratch.numel() >= 8 * n * 4):
+            raise ValueError("scratch must be a contiguous int64 tensor of at least 8 x n x 4 elements")
+        out = torch.empty((4, n, 4), dtype=torch.int64, device=self.device)
+        p = _lib.QuotientPolysC()
+        for j in range(4):
+            p.w[j] = polys[j].data_ptr()
+            p.sigma[j] = polys[5 + j].data_ptr()
+        p.z = polys[4].data_ptr()
+        for i, s in enumerate(self.QUOTIENT_SELECTORS):
+            setattr(p, s, polys[9 + i].data_ptr())
+        p.pi = None if pi is None else pi.data_ptr()
+        zeta = domain_generator(log2_n + 2) if omega_4n is None else _field(omega_4n)
+        ks = (_lib.Scalar * 4)(*[_field(x).c for x in k])
+        st = self._lib.pg_quotient(self._h, log2_n, C.byref(p), C.byref(_field(alpha).c), C.byref(_field(beta).c),
+                                   C.byref(_field(gamma).c), C.byref(zeta.c), ks, C.byref(_field(g).c), out.data_ptr(),
+                                   scratch.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_quotient")
+        return out
+
+    def evaluate(self, polys: torch.Tensor, point) -> list:
+        """the polynomials at a point (pg_poly_evaluate, the prover's round 4): polys int64[n, 4] or int64[c, n, 4] coefficients
+        on the device (rows of 4 contiguous limbs; n any size >= 1) -> c BlsScalars sum_i p_i point^i"""
+        if not (self._rows(polys) and polys.dim() in (2, 3)):
+            raise ValueError("polys must be int64[n, 4] or int64[c, n, 4] on the device with contiguous rows")
+        cols = polys.shape[0] if polys.dim() == 3 else 1
+        n = polys.shape[-2]
+        stride = polys.stride(0) // 4 if polys.dim() == 3 and cols > 1 else n
+        if polys.dim() == 3 and cols > 1 and polys.stride(0) % 4:
+            raise ValueError("the columns of polys must start on whole rows")
+        out = torch.empty((cols, 4), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_poly_evaluate(self._h, polys.data_ptr(), cols, stride, n, C.byref(_field(point).c), out.data_ptr(),
+                                        self._stream())
+        if st != 0:
+            raise PgError(st, "pg_poly_evaluate")
+        return [BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in row]) for row in out.cpu().tolist()]
+
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
         """(num_bits int32[batch], row_off int64[batch+1], var_off int64[batch+1]) for the *_plan calls"""
