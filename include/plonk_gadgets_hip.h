@@ -580,6 +580,32 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
 pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_cols, uint64_t col_stride, uint64_t n,
                            const pg_scalar *point, pg_scalar *d_out, void *stream);
 
+/* ---- commitments: BLS12-381 G1 and the multi-scalar multiplication -------------------------------
+ * pg_g1_affine: a point of G1 (y^2 = x^3 + 4 over the base field Fq, p = 0x1a0111ea...ffffaaab) in affine coordinates, each
+ * coordinate 6 little-endian 64-bit limbs in Montgomery form (R = 2^384), fully reduced below p; (0, 0) is the identity.
+ * 96 bytes; device arrays of them must be 16-byte aligned. */
+typedef struct pg_g1_affine { uint64_t x[6], y[6]; } pg_g1_affine;
+/* pg_msm: d_out[j] = sum_{i < n} s_j[i] P_i for the n_cols scalar columns s_j = d_scalars + j * col_stride (device, Montgomery
+ * form, fully reduced) against the same n bases P_i = d_bases[i] (device).  Outputs are normalised affine points, so the
+ * limbs do not depend on the order of summation.  1 <= n < 2^31, col_stride >= n.  Bases not on the curve are the caller's
+ * problem: the sum is then meaningless (nothing is checked on the device).  n = 0, a stride below n, a NULL or misaligned
+ * pointer, or d_out overlapping an input -> PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise the call only enqueues.
+ * Pippenger with 16 windows of signed 16-bit digits.  Device memory the engine keeps for it (grow-only): 16 n bytes of sort
+ * keys and values, the sort's temporary storage, 2 ceil(n / 64) (4 + 192) bytes of partial bucket sums (and 1/32 of that
+ * again), 16 (2^15 + 1) x 192 bytes of buckets and ~1 MB of per-window sums: about 5.6 GiB at n = 2^28. */
+pg_status pg_msm(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_scalars, uint64_t n, uint64_t n_cols,
+                 uint64_t col_stride, pg_g1_affine *d_out, void *stream);
+/* pg_srs_setup: d_out[i] = tau^i * base for i < n (1 <= n <= 2^32), base == NULL meaning the generator G.  This is
+ * dusk-plonk's PublicParameters::setup `powers_of_g` with the secret tau chosen by the caller: INSECURE, for development
+ * and tests only (whoever knows tau can forge proofs).  tau (host, Montgomery form) = 0 or not reduced, a base (host) that
+ * is the identity or not reduced, a NULL or misaligned d_out -> PG_ERR_INVALID_ARGUMENT.  Enqueues only.  Device memory the
+ * engine keeps for it (grow-only): 2.3 MiB of fixed-base tables and 384 MiB for a chunk of 2^21 points. */
+pg_status pg_srs_setup(pg_engine *e, const pg_scalar *tau, const pg_g1_affine *base, uint64_t n, pg_g1_affine *d_out, void *stream);
+/* pg_g1_to_compressed (host only): the 48-byte zcash / dusk-bls12_381 encoding of `count` points, out[48 i ...]: x big-endian,
+ * bit 7 of the first byte set (compressed), bit 6 for the identity (then every other bit is 0), bit 5 when y > (p - 1) / 2.
+ * NULL pointers with count > 0, or coordinates not reduced -> PG_ERR_INVALID_ARGUMENT. */
+pg_status pg_g1_to_compressed(const pg_g1_affine *in, uint64_t count, uint8_t *out);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

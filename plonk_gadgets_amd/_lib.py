@@ -57,6 +57,11 @@ class QuotientPolysC(C.Structure):
         (n, C.c_void_p) for n in ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "pi")]
 
 
+class G1AffineC(C.Structure):
+    """pg_g1_affine: x and y, six Montgomery limbs each"""
+    _fields_ = [("x", C.c_uint64 * 6), ("y", C.c_uint64 * 6)]
+
+
 # every symbol include/plonk_gadgets_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -193,6 +198,9 @@ SIGNATURES = {
     "pg_quotient": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar),
                               _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_poly_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p]),
+    "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_srs_setup": (C.c_int, [C.c_void_p, _P(Scalar), _P(G1AffineC), C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_g1_to_compressed": (C.c_int, [_P(G1AffineC), C.c_uint64, C.c_void_p]),
     "pg_shard_range": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64)]),
     "pg_range_check_shard_layout": (C.c_int, [_P(Scalar), _P(Scalar), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                               _P(ShardC)]),

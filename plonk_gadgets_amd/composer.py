@@ -445,6 +445,24 @@ class StandardComposer:
         x[:n] = self.construct_dense_pi_vec()
         return self.engine.ifft(x, inplace=True)
 
+    SIGMAS = ("left_sigma", "right_sigma", "out_sigma", "fourth_sigma")
+
+    def preprocessed_commitments(self, ck, padded_n: int | None = None) -> dict:
+        """the commitment half of dusk-plonk's prover.preprocess(&ck): the commitments (G1Affine) of the eleven SELECTORS and
+        of the four sigma polynomials (SIGMAS), keyed by name, under the CommitKey ck.  Raises PolynomialDegreeTooLarge when
+        padded_n exceeds the key."""
+        padded_n = self._padded_n(padded_n)
+        if padded_n > ck.powers.shape[0]:
+            from .g1 import PolynomialDegreeTooLarge
+            raise PolynomialDegreeTooLarge(f"padded_n = {padded_n} > the key's {ck.powers.shape[0]} powers")
+        sel = self.selector_polynomials(padded_n)
+        x = torch.stack([sel[name] for name in self.SELECTORS])
+        del sel
+        out = dict(zip(self.SELECTORS, ck.commit(x)))
+        del x
+        out.update(zip(self.SIGMAS, ck.commit(self.sigma_polynomials(padded_n))))
+        return out
+
     NON_ARITHMETIC_SELECTORS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
 
     def prover_polynomials(self, beta, gamma, padded_n: int | None = None) -> dict:

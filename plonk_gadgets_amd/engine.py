@@ -590,6 +590,28 @@ class Engine:
             raise PgError(st, "pg_poly_evaluate")
         return [BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in row]) for row in out.cpu().tolist()]
 
+    def msm(self, bases: torch.Tensor, scalars: torch.Tensor) -> list:
+        """sum_i s_i P_i (pg_msm): bases int64[n, 12] (pg_g1_affine rows on the device), scalars int64[n, 4] or int64[c, n, 4]
+        (Montgomery form, rows of 4 contiguous limbs, the columns at any whole-row stride) -> c G1Affines"""
+        from .g1 import points_of
+        if not (bases.dim() == 2 and bases.shape[1] == 12 and bases.dtype == torch.int64 and bases.device == self.device
+                and bases.is_contiguous()):
+            raise ValueError("bases must be a contiguous int64[n, 12] tensor on the engine's device")
+        if not (self._rows(scalars) and scalars.dim() in (2, 3)):
+            raise ValueError("scalars must be int64[n, 4] or int64[c, n, 4] on the device with contiguous rows")
+        cols = scalars.shape[0] if scalars.dim() == 3 else 1
+        n = scalars.shape[-2]
+        if n != bases.shape[0]:
+            raise ValueError(f"{n} scalars per column for {bases.shape[0]} bases")
+        stride = scalars.stride(0) // 4 if scalars.dim() == 3 and cols > 1 else n
+        if scalars.dim() == 3 and cols > 1 and scalars.stride(0) % 4:
+            raise ValueError("the columns of scalars must start on whole rows")
+        out = torch.empty((cols, 12), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_msm(self._h, bases.data_ptr(), scalars.data_ptr(), n, cols, stride, out.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_msm")
+        return points_of(out)
+
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
         """(num_bits int32[batch], row_off int64[batch+1], var_off int64[batch+1]) for the *_plan calls"""
