@@ -606,6 +606,24 @@ pg_status pg_srs_setup(pg_engine *e, const pg_scalar *tau, const pg_g1_affine *b
  * NULL pointers with count > 0, or coordinates not reduced -> PG_ERR_INVALID_ARGUMENT. */
 pg_status pg_g1_to_compressed(const pg_g1_affine *in, uint64_t count, uint8_t *out);
 
+/* ---- openings: the prover's round 5 ---------------------------------------------------------------
+ * Both calls take n_cols (1..32) columns p_j = d_cols[j] of n coefficients each (device, Montgomery form, 1 <= n <= 2^32) as a
+ * HOST array of device pointers, which may repeat (one column can carry two weights), and n_cols host weights mu[j]; f is
+ * sum_j mu_j p_j.
+ * pg_poly_open: dusk-plonk 0.8's CommitKey::compute_aggregate_witness followed by Polynomial::ruffini [DEP-RECALL] (mu_j = v^j
+ * there; here mu may also carry the xi^(jn) factors that assemble t from its parts).  d_witness[i] = q_i for i < n - 1, where
+ * f = q (X - point) + f(point): q_{n-2} = f_{n-1}, q_{i-1} = f_i + point q_i; d_witness[n - 1] = 0, so the witness is a plain
+ * n-coefficient column CommitKey.commit takes as is.  d_value (device, one scalar) = f(point).
+ * pg_poly_combine: d_out = f (n coefficients), nothing divided.
+ * A NULL or misaligned pointer, n_cols or n out of range, a weight or point not reduced below the modulus, an output that
+ * overlaps an input column (or d_value overlapping d_witness) -> PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise the
+ * calls only enqueue on `stream`.  Device memory the engine keeps for pg_poly_open (grow-only): ceil(n / 2048) x 32 bytes of
+ * tile totals (4 MiB at n = 2^28).  pg_poly_combine keeps none. */
+pg_status pg_poly_open(pg_engine *e, const pg_scalar *const *d_cols, const pg_scalar *mu, uint64_t n_cols, uint64_t n,
+                       const pg_scalar *point, pg_scalar *d_witness, pg_scalar *d_value, void *stream);
+pg_status pg_poly_combine(pg_engine *e, const pg_scalar *const *d_cols, const pg_scalar *mu, uint64_t n_cols, uint64_t n,
+                          pg_scalar *d_out, void *stream);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

@@ -201,6 +201,9 @@ SIGNATURES = {
     "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_srs_setup": (C.c_int, [C.c_void_p, _P(Scalar), _P(G1AffineC), C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_g1_to_compressed": (C.c_int, [_P(G1AffineC), C.c_uint64, C.c_void_p]),
+    "pg_poly_open": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p,
+                               C.c_void_p]),
+    "pg_poly_combine": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_shard_range": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64)]),
     "pg_range_check_shard_layout": (C.c_int, [_P(Scalar), _P(Scalar), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                               _P(ShardC)]),

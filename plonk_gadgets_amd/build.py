@@ -10,8 +10,8 @@ CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplonk_gadgets_hip.so")
 SOURCES = ["capi.hip"]
 HEADERS = ["experiment.hpp", "fr.hpp", "emit.hpp", "invert.hpp", "range_gadgets.hpp", "scalar_gadgets.hpp", "composer.hpp", "permutation.hpp", "materialize.hpp",
-           "permutation_product.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp", "msm.hpp",
-           "capi_composer.inc", "capi_dist.inc", "capi_msm.inc"]
+           "permutation_product.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp", "msm.hpp", "opening.hpp",
+           "capi_composer.inc", "capi_dist.inc", "capi_msm.inc", "capi_open.inc"]
 
 
 def hipcc() -> str:

@@ -506,6 +506,16 @@ class StandardComposer:
         """the quotient polynomial t as int64[4, padded_n, 4] (t_lo, t_mid, t_hi, t_4th): Engine.quotient of prover_polynomials()"""
         return self.engine.quotient(**self.prover_polynomials(beta, gamma, padded_n), alpha=alpha, beta=beta, gamma=gamma)
 
+    def prove(self, ck, label=b"plonk", preprocessed: dict | None = None, timings: dict | None = None):
+        """a PLONK proof (proof.Proof) of the circuit as it stands, padded to the next power of two, under the CommitKey ck:
+        dusk-plonk 0.8's Prover::prove [DEP-RECALL] with the transcript label `label` (Prover::default()'s is b"plonk").
+        preprocessed: the dict of preprocessed_commitments(ck), so that proving the same circuit again (after clear_witness)
+        does not repeat its 15 MSMs.  timings: a dict that receives each phase's milliseconds (the device synchronised between
+        phases).  Without blinding the proof is NOT zero-knowledge.  Raises PolynomialDegreeTooLarge when the
+        padded circuit exceeds the key, ValueError for the widgets the quotient leaves out."""
+        from .proof import prove
+        return prove(self, ck, label, preprocessed, timings)
+
 @dataclass
 class AllocatedScalar:
     """/root/reference/src/allocated_scalar.rs:17-30"""

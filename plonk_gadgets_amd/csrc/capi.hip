@@ -142,6 +142,9 @@ struct pg_engine {
     // scratch of pg_msm (sort keys, partial and bucket sums) and of pg_srs_setup (fixed-base tables, a chunk of points): grow-only
     uint4 *d_msm = nullptr, *d_srs = nullptr;
     uint64_t msm_units = 0, srs_units = 0;  // (16-byte units)
+    // scratch of pg_poly_open (grow-only): its tile totals and carries
+    uint4 *d_open = nullptr;
+    uint64_t open_units = 0;  // (16-byte units)
 };
 
 namespace {
@@ -589,6 +592,7 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->d_eval) (void)hipFree(e->d_eval);
     if (e->d_msm) (void)hipFree(e->d_msm);
     if (e->d_srs) (void)hipFree(e->d_srs);
+    if (e->d_open) (void)hipFree(e->d_open);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
@@ -1611,3 +1615,4 @@ pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_c
 #include "capi_composer.inc"
 #include "capi_dist.inc"
 #include "capi_msm.inc"
+#include "capi_open.inc"

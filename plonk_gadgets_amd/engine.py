@@ -590,6 +590,45 @@ class Engine:
             raise PgError(st, "pg_poly_evaluate")
         return [BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in row]) for row in out.cpu().tolist()]
 
+    # ---- openings: the prover's round 5 ---------------------------------------------------------------------------
+    def _columns(self, polys, mu):
+        """polys (a list of int64[n, 4] device tensors, or int64[c, n, 4]) and their weights -> (pointer array, weight array,
+        c, n, the tensors kept alive)"""
+        cols = list(polys.unbind(0)) if isinstance(polys, torch.Tensor) and polys.dim() == 3 else list(polys)
+        if not cols:
+            raise ValueError("no columns")
+        n = cols[0].shape[0]
+        for t in cols:
+            if not (self._rows(t) and t.dim() == 2 and t.shape[0] == n):
+                raise ValueError(f"every column must be int64[{n}, 4] on the device with contiguous rows")
+        mu = list(mu)
+        if len(mu) != len(cols):
+            raise ValueError(f"{len(mu)} weights for {len(cols)} columns")
+        ptrs = (C.c_void_p * len(cols))(*[t.data_ptr() for t in cols])
+        ws = (_lib.Scalar * len(cols))(*[_field(m).c for m in mu])
+        return ptrs, ws, len(cols), n, cols
+
+    def open(self, polys, mu, point):
+        """the KZG opening of f = sum_j mu_j p_j at `point` (pg_poly_open: CommitKey::compute_aggregate_witness then
+        Polynomial::ruffini) -> (witness int64[n, 4], f(point) as a BlsScalar): f = witness (X - point) + f(point), the witness's
+        top coefficient 0.  polys: up to 32 int64[n, 4] device tensors (they may repeat) or an int64[c, n, 4] tensor."""
+        ptrs, ws, c, n, keep = self._columns(polys, mu)
+        w = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        v = torch.empty((1, 4), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_poly_open(self._h, ptrs, ws, c, n, C.byref(_field(point).c), w.data_ptr(), v.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_poly_open")
+        return w, BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in v[0].tolist()])
+
+    def combine(self, polys, mu) -> torch.Tensor:
+        """sum_j mu_j p_j as int64[n, 4] (pg_poly_combine); polys as for open"""
+        ptrs, ws, c, n, keep = self._columns(polys, mu)
+        out = torch.empty((n, 4), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_poly_combine(self._h, ptrs, ws, c, n, out.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_poly_combine")
+        return out
+
     def msm(self, bases: torch.Tensor, scalars: torch.Tensor) -> list:
         """sum_i s_i P_i (pg_msm): bases int64[n, 12] (pg_g1_affine rows on the device), scalars int64[n, 4] or int64[c, n, 4]
         (Montgomery form, rows of 4 contiguous limbs, the columns at any whole-row stride) -> c G1Affines"""

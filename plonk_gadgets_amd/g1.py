@@ -74,6 +74,27 @@ class G1Affine:
             raise PgError(st, "pg_g1_to_compressed")
         return bytes(out)
 
+    @staticmethod
+    def from_compressed(data: bytes) -> "G1Affine":
+        """the inverse of to_compressed (host integers: y = (x^3 + 4)^((p + 1) / 4), the sign from bit 5); raises ValueError on
+        an encoding that is not compressed, not canonical or not on the curve"""
+        if len(data) != 48 or not data[0] & 0x80:
+            raise ValueError("not a 48-byte compressed G1 encoding")
+        if data[0] & 0x40:
+            if data[0] != 0xC0 or any(data[1:]):
+                raise ValueError("a non-canonical encoding of the identity")
+            return G1Affine.identity()
+        x = int.from_bytes(bytes([data[0] & 0x1F]) + data[1:], "big")
+        if x >= P:
+            raise ValueError("x is not reduced")
+        rhs = (x * x * x + 4) % P
+        y = pow(rhs, (P + 1) // 4, P)
+        if y * y % P != rhs:
+            raise ValueError("not on the curve")
+        if bool(data[0] & 0x20) != (y > (P - 1) // 2):
+            y = P - y
+        return G1Affine.from_ints(x, y)
+
     def __eq__(self, other) -> bool:
         return isinstance(other, G1Affine) and self.limbs == other.limbs
 
@@ -135,3 +156,13 @@ class CommitKey:
             raise PolynomialDegreeTooLarge(f"a polynomial of {n} coefficients > the key's {self.powers.shape[0]} powers")
         out = self.engine.msm(self.powers[:n], polys)
         return out[0] if polys.dim() == 2 else out
+
+    def aggregate_witness(self, polys, point, v):
+        """dusk-plonk's CommitKey::compute_aggregate_witness then ruffini: the opening witness of sum_j v^j p_j at `point`
+        (Engine.open with mu_j = v^j) -> (witness int64[n, 4], the combination's value at point)"""
+        from .engine import _field
+        c = polys.shape[0] if isinstance(polys, torch.Tensor) and polys.dim() == 3 else len(polys)
+        vv, mu = _field(v), []
+        for j in range(c):
+            mu.append(_field(1) if j == 0 else mu[-1] * vv)
+        return self.engine.open(polys, mu, point)
