@@ -624,6 +624,44 @@ pg_status pg_poly_open(pg_engine *e, const pg_scalar *const *d_cols, const pg_sc
 pg_status pg_poly_combine(pg_engine *e, const pg_scalar *const *d_cols, const pg_scalar *mu, uint64_t n_cols, uint64_t n,
                           pg_scalar *d_out, void *stream);
 
+/* ---- verification: BLS12-381 G2 on the host and the pairing check on the device ---------------------
+ * pg_g2_affine: a point of G2, the order-r subgroup of the twist y^2 = x^3 + 4 (1 + u) over Fq2 = Fq[u] / (u^2 + 1), in affine
+ * coordinates x.c0, x.c1, y.c0, y.c1, each 6 little-endian 64-bit limbs in Montgomery form, fully reduced; all zero is the
+ * identity.  192 bytes.  G2 arithmetic is host-only: it happens once per key, never per proof. */
+typedef struct pg_g2_affine { uint64_t x[12], y[12]; } pg_g2_affine;
+/* a G2 point prepared for pairings: the 68 line functions of the ate Miller loop over it, on the engine's device */
+typedef struct pg_g2_prepared pg_g2_prepared;
+/* pg_g2_mul (host only): *out = k * p, p == NULL meaning the generator of G2 [DEP-RECALL]; k in Montgomery form.  Affine
+ * double-and-add, a few milliseconds.  NULL k or out, k or a coordinate not reduced, p not on the twist ->
+ * PG_ERR_INVALID_ARGUMENT.  Membership of the order-r subgroup is not tested: (r - 1) p == -p is that test. */
+pg_status pg_g2_mul(const pg_g2_affine *p, const pg_scalar *k, pg_g2_affine *out);
+/* pg_g2_to_compressed (host only): the 96-byte zcash / dusk-bls12_381 encoding of `count` points, out[96 i ...]: x.c1 then x.c0,
+ * big-endian; in the first byte bit 7 set (compressed), bit 6 for the identity (then every other bit is 0), bit 5 when y is
+ * the larger of (y, -y), compared by c1 first and then by c0.  NULL pointers with count > 0, or coordinates not reduced ->
+ * PG_ERR_INVALID_ARGUMENT. */
+pg_status pg_g2_to_compressed(const pg_g2_affine *in, uint64_t count, uint8_t *out);
+/* pg_g2_prepare: runs the doubling and addition steps of the ate loop over |x| = 0xd201000000010000 on the host and uploads
+ * the 68 lines (2 Fq2 each: 13 056 bytes) to the engine's device; synchronous.  *out is released with
+ * pg_g2_prepared_destroy, before the engine.  q must be on the twist and of order r (the first is checked, the second is the
+ * caller's duty); the identity, a point off the twist, coordinates not reduced or a NULL -> PG_ERR_INVALID_ARGUMENT. */
+pg_status pg_g2_prepare(pg_engine *e, const pg_g2_affine *q, pg_g2_prepared **out);
+void pg_g2_prepared_destroy(pg_g2_prepared *p);
+/* pg_pairing_check: d_ok[i] = 1 if prod_{j < n_pairs} e(P_ij, Q_j) == 1, else 0, for the n_checks rows P_i of
+ * d_points[n_checks][n_pairs] (device; on the curve and in G1 -- nothing is checked on the device; an identity P contributes
+ * 1) against the same n_pairs prepared points (a HOST array of handles).  Per check: one Miller loop that accumulates all
+ * pairs into one value, one final exponentiation.  1 <= n_pairs <= 8 (the points of a check are staged in LDS that the final
+ * exponentiation reuses; a KZG check needs 2); n_checks = 0 does nothing.  Six lanes share a check and a workgroup of 252
+ * carries 42, so n_checks = 1 is one workgroup: a single check is bound by latency (about 9 000 dependent Fq products).
+ * NULL or misaligned pointers, n_pairs out of range, n_checks > 2^31, a handle of another device -> PG_ERR_INVALID_ARGUMENT
+ * with nothing launched; otherwise the call only enqueues.  Keeps no device memory.
+ * pg_pairing_gt: the GT values themselves, d_gt[i] = 72 limbs: the six Fq2 coefficients over w^0 .. w^5 (w^6 = 1 + u) of
+ * (prod_j e(P_ij, Q_j))^3, where e is the ate pairing with the plain final power (p^12 - 1) / r -- the hard part's addition
+ * chain computes the cube, which is 1 exactly when the product is.  For tests and for callers that compare values. */
+pg_status pg_pairing_check(pg_engine *e, const pg_g1_affine *d_points, const pg_g2_prepared *const *prepared, uint64_t n_checks,
+                           uint64_t n_pairs, uint8_t *d_ok, void *stream);
+pg_status pg_pairing_gt(pg_engine *e, const pg_g1_affine *d_points, const pg_g2_prepared *const *prepared, uint64_t n_checks,
+                        uint64_t n_pairs, uint64_t *d_gt, void *stream);
+
 /* ---- multi-GPU: shards, packed chunks, the all-gather (BASELINE.json config 5) -------------
  * The reference has no counterpart: it is single-threaded (`&mut StandardComposer`, src/range.rs:27-32).  What is
  * sharded is the loop  for w in witnesses { allocate; range_check }  of tests/range_gadgets_tests.rs:29-44: items are

@@ -62,6 +62,11 @@ class G1AffineC(C.Structure):
     _fields_ = [("x", C.c_uint64 * 6), ("y", C.c_uint64 * 6)]
 
 
+class G2AffineC(C.Structure):
+    """pg_g2_affine: x and y over Fq2 (c0 then c1), six Montgomery limbs each"""
+    _fields_ = [("x", C.c_uint64 * 12), ("y", C.c_uint64 * 12)]
+
+
 # every symbol include/plonk_gadgets_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -204,6 +209,12 @@ SIGNATURES = {
     "pg_poly_open": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "pg_poly_combine": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_g2_mul": (C.c_int, [_P(G2AffineC), _P(Scalar), _P(G2AffineC)]),
+    "pg_g2_to_compressed": (C.c_int, [_P(G2AffineC), C.c_uint64, C.c_void_p]),
+    "pg_g2_prepare": (C.c_int, [C.c_void_p, _P(G2AffineC), _P(C.c_void_p)]),
+    "pg_g2_prepared_destroy": (None, [C.c_void_p]),
+    "pg_pairing_check": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_pairing_gt": (C.c_int, [C.c_void_p, C.c_void_p, _P(C.c_void_p), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_shard_range": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, _P(C.c_uint64), _P(C.c_uint64)]),
     "pg_range_check_shard_layout": (C.c_int, [_P(Scalar), _P(Scalar), C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64,
                                               _P(ShardC)]),

@@ -463,6 +463,12 @@ class StandardComposer:
         out.update(zip(self.SIGMAS, ck.commit(self.sigma_polynomials(padded_n))))
         return out
 
+    def verifier_key(self, ck, padded_n: int | None = None):
+        """the VerifierKey of the circuit as it stands: the padded size and preprocessed_commitments(ck, padded_n)"""
+        from .verifier import VerifierKey
+        padded_n = self._padded_n(padded_n)
+        return VerifierKey(padded_n, self.preprocessed_commitments(ck, padded_n))
+
     NON_ARITHMETIC_SELECTORS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
 
     def prover_polynomials(self, beta, gamma, padded_n: int | None = None) -> dict:

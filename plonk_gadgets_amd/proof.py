@@ -76,6 +76,11 @@ class Proof:
             kw[f] = BlsScalar.from_int(v)
         return Proof(**kw)
 
+    def verify(self, vk, ok, public_inputs=None, label=b"plonk") -> bool:
+        """verifier.verify: True iff this proof verifies under the VerifierKey vk and the OpeningKey ok"""
+        from .verifier import verify
+        return verify(self, vk, ok, public_inputs, label)
+
 
 assert [f.name for f in fields(Proof)] == list(COMMITMENTS + EVALUATIONS)
 

@@ -1,0 +1,322 @@
+"""The pairing-based verifier of proof.Proof: VerifierKey, verify, verify_batch, verify_each.  DESIGN section 3.13.
+
+The algebra is dusk-plonk 0.8's Proof::verify [DEP-RECALL]: the transcript of prove() replayed, PI(xi) by Lagrange evaluation,
+t(xi) from N(xi) = t(xi) Z_H(xi), [r] from the key's commitments with the proof's q_arith(xi), the two KZG openings (at xi and
+xi omega) folded by the separation challenge u into ONE check
+    e(W_xi + u W_xiw, [tau]_2) e(-(xi W_xi + u xi omega W_xiw + F - E g), [1]_2) = 1,   F = F_xi + u F_xiw,  E = E_xi + u E_xiw.
+Both G1 arguments are linear combinations of the same ~27 points: one Engine.msm call with two scalar columns gives both,
+then one pg_pairing_check of two pairs.  Everything a proof can get wrong makes verify return False; it never raises for it.
+
+Subgroup: G1Affine.from_compressed tests the curve equation only, so every commitment of a proof is tested here for r P = O,
+by a Jacobian double-and-add over Python integers (about 4 ms per point, cached; the key's 15 commitments are tested once).
+That is the simplest means this package has, not a fast one -- pg_msm sums, it cannot multiply eleven points by r separately
+-- and about as costly as the MSM of a single verify; the first follow-up is the endomorphism test (Bowe, 2019: half the
+doublings) or a batched r P through the device's G1 code.
+
+verify_batch folds the proofs' two sides with 128-bit weights drawn from `secrets` AFTER the proofs are fixed: if some proof's
+check e(A_i, [tau]_2) e(B_i, [1]_2) is not 1, the folded product is a non-zero polynomial of degree 1 in each weight over GT
+(a group of prime order r), so it is 1 with probability at most 2^-128.  Weights from the OS rather than from a transcript over
+all proofs: nothing then depends on every verifier hashing the same bytes in the same order, and a verifier has no reason to
+be deterministic.  verify_each runs one two-column MSM per proof (a segmented pass does not exist in pg_msm) and then one
+pg_pairing_check of len(proofs) checks: the call that names the bad proof."""
+from __future__ import annotations
+
+import ctypes as C
+import functools
+import secrets
+
+import torch
+
+from .engine import DEFAULT_K, PgError, domain_generator
+from .g1 import P, G1Affine, points_tensor
+from .proof import COMMITMENTS, EVALUATIONS, Proof
+from .scalar import BlsScalar
+from .transcript import R, Transcript
+
+SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
+SIGMAS = ("left_sigma", "right_sigma", "out_sigma", "fourth_sigma")
+MAX_PAIRS = 8
+
+
+# ---- G1 membership ----------------------------------------------------------------------------------------------------------
+@functools.lru_cache(maxsize=1 << 16)
+def _valid_limbs(limbs) -> bool:
+    p = G1Affine(limbs).to_ints()
+    if p is None:
+        return True
+    # Montgomery limbs at or above p stand for the same residue, but pg_msm refuses them: not a valid point here either
+    if any(sum(w << (64 * i) for i, w in enumerate(limbs[6 * h:6 * h + 6])) >= P for h in (0, 1)):
+        return False
+    x, y = p
+    if (y * y - x * x * x - 4) % P:
+        return False
+    # r P in Jacobian coordinates (dbl-2009-l, add-2007-bl with Z2 = 1)
+    X, Y, Z = x, y, 1
+    for bit in bin(R)[3:]:
+        if Z:
+            A, B = X * X % P, Y * Y % P
+            Cq = B * B % P
+            D = 2 * ((X + B) ** 2 - A - Cq) % P
+            E = 3 * A % P
+            X3 = (E * E - 2 * D) % P
+            X, Y, Z = X3, (E * (D - X3) - 8 * Cq) % P, 2 * Y * Z % P
+        if bit == "1":
+            if not Z:
+                X, Y, Z = x, y, 1
+                continue
+            ZZ = Z * Z % P
+            U2, S2 = x * ZZ % P, y * Z * ZZ % P
+            if U2 == X:
+                if S2 != Y:
+                    X, Y, Z = 1, 1, 0
+                    continue
+                return False  # (a doubling inside the ladder: only a point of tiny order gets here)
+            H, r = (U2 - X) % P, (S2 - Y) % P
+            HH = H * H % P
+            HHH, V = H * HH % P, X * HH % P
+            X3 = (r * r - HHH - 2 * V) % P
+            X, Y, Z = X3, (r * (V - X3) - Y * HHH) % P, Z * H % P
+    return Z == 0
+
+
+def g1_in_subgroup(p: G1Affine) -> bool:
+    """on y^2 = x^3 + 4 and of order dividing r (the identity included)"""
+    return _valid_limbs(p.limbs)
+
+
+# ---- the pairing check ------------------------------------------------------------------------------------------------------
+def _prepared_array(prepared):
+    arr = (C.c_void_p * len(prepared))(*[p._h for p in prepared])
+    return arr
+
+
+def pairing_check(engine, points: torch.Tensor, prepared) -> torch.Tensor:
+    """pg_pairing_check: points int64[n_checks, n_pairs, 12] on the engine's device, prepared a list of n_pairs PreparedG2 ->
+    uint8[n_checks], 1 where prod_j e(P_ij, Q_j) = 1"""
+    if not (points.dim() == 3 and points.shape[2] == 12 and points.dtype == torch.int64 and points.device == engine.device
+            and points.is_contiguous() and points.shape[1] == len(prepared)):
+        raise ValueError("points must be a contiguous int64[n_checks, len(prepared), 12] tensor on the engine's device")
+    out = torch.empty((points.shape[0],), dtype=torch.uint8, device=engine.device)
+    st = engine._lib.pg_pairing_check(engine._h, points.data_ptr(), _prepared_array(prepared), points.shape[0], points.shape[1],
+                                      out.data_ptr(), engine._stream())
+    if st != 0:
+        raise PgError(st, "pg_pairing_check")
+    return out
+
+
+def pairing_gt(engine, points: torch.Tensor, prepared) -> torch.Tensor:
+    """pg_pairing_gt: the GT values (prod_j e(P_ij, Q_j))^3 as int64[n_checks, 72] (six Fq2 coefficients over w^k)"""
+    if not (points.dim() == 3 and points.shape[2] == 12 and points.dtype == torch.int64 and points.device == engine.device
+            and points.is_contiguous() and points.shape[1] == len(prepared)):
+        raise ValueError("points must be a contiguous int64[n_checks, len(prepared), 12] tensor on the engine's device")
+    out = torch.empty((points.shape[0], 72), dtype=torch.int64, device=engine.device)
+    st = engine._lib.pg_pairing_gt(engine._h, points.data_ptr(), _prepared_array(prepared), points.shape[0], points.shape[1],
+                                   out.data_ptr(), engine._stream())
+    if st != 0:
+        raise PgError(st, "pg_pairing_gt")
+    return out
+
+
+# ---- the key ----------------------------------------------------------------------------------------------------------------
+class VerifierKey:
+    """the padded circuit size n and the 15 preprocessed commitments (SELECTORS then SIGMAS).  The transcript absorbs all 15;
+    [r] uses q_m, q_l, q_r, q_o, q_4, q_c and fourth_sigma; the xi opening left / right / out_sigma, q_arith, q_c, q_l, q_r."""
+    NAMES = SELECTORS + SIGMAS
+    SIZE = 8 + 48 * len(NAMES)
+
+    def __init__(self, n: int, commitments: dict):
+        if n < 1 or n & (n - 1):
+            raise ValueError("n must be a power of two")
+        if set(commitments) != set(self.NAMES):
+            raise ValueError("a verifier key holds exactly the 15 preprocessed commitments")
+        self.n = int(n)
+        self.commitments = {k: commitments[k] for k in self.NAMES}
+        # tested once, here: verify() trusts its key
+        self.valid = all(g1_in_subgroup(c) for c in self.commitments.values())
+
+    def to_bytes(self) -> bytes:
+        return self.n.to_bytes(8, "little") + b"".join(self.commitments[k].to_compressed() for k in self.NAMES)
+
+    @staticmethod
+    def from_bytes(data: bytes) -> "VerifierKey":
+        if len(data) != VerifierKey.SIZE:
+            raise ValueError(f"a verifier key is {VerifierKey.SIZE} bytes, not {len(data)}")
+        n = int.from_bytes(data[:8], "little")
+        return VerifierKey(n, {k: G1Affine.from_compressed(data[8 + 48 * i:56 + 48 * i]) for i, k in enumerate(VerifierKey.NAMES)})
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, VerifierKey) and self.n == other.n and self.commitments == other.commitments
+
+
+# ---- one proof's two sides ---------------------------------------------------------------------------------------------------
+def _pi_at(pi: dict, xi: int, n: int, omega: int, zh: int) -> int:
+    acc = 0
+    for i, v in pi.items():
+        wi = pow(omega, int(i), R)
+        acc += int(v) * wi * zh * pow(n * (xi - wi) % R, -1, R)
+    return acc % R
+
+
+def _as_ints(public_inputs) -> dict:
+    out = {}
+    for i, v in (public_inputs or {}).items():
+        out[int(i)] = v.to_int() if isinstance(v, BlsScalar) else int(v) % R
+    return out
+
+
+def sides(proof: Proof, vk: VerifierKey, ok, public_inputs, label=b"plonk"):
+    """None when the proof is rejected before any pairing, else {point: [a, b]}: the check is
+    e(sum a P, [tau]_2) e(sum b P, [1]_2) = 1"""
+    if not vk.valid:
+        return None
+    cm = {f: getattr(proof, f) for f in COMMITMENTS}
+    if not all(g1_in_subgroup(c) for c in cm.values()):
+        return None
+    ev = {f: getattr(proof, f).to_int() for f in EVALUATIONS}
+    pre, n = vk.commitments, vk.n
+    m = n.bit_length() - 1
+    omega = domain_generator(m).to_int()
+    tr = Transcript(label)
+    tr.circuit_domain_sep(n)
+    for name in SELECTORS + SIGMAS:
+        tr.append_commitment(name.encode(), pre[name])
+    for lab, f in zip((b"w_l", b"w_r", b"w_o", b"w_4"), ("a_comm", "b_comm", "c_comm", "d_comm")):
+        tr.append_commitment(lab, cm[f])
+    beta = tr.challenge_int(b"beta")
+    tr.append_scalar(b"beta", beta)
+    gamma = tr.challenge_int(b"gamma")
+    tr.append_commitment(b"z", cm["z_comm"])
+    alpha = tr.challenge_int(b"alpha")
+    for j in range(4):
+        tr.append_commitment(b"t_%d" % (j + 1), cm["t_%d_comm" % (j + 1)])
+    xi = tr.challenge_int(b"z")
+    for f in EVALUATIONS:
+        tr.append_scalar(f.encode(), ev[f])
+    v = tr.challenge_int(b"aggregate_witness")
+    tr.append_commitment(b"w_z", cm["w_z_comm"])
+    v2 = tr.challenge_int(b"aggregate_witness")
+    tr.append_commitment(b"w_z_w", cm["w_zw_comm"])
+    u = tr.challenge_int(b"seperation challenge")  # (dusk's spelling) [DEP-RECALL]
+
+    xin = pow(xi, n, R)
+    if xin == 1:
+        return None
+    a, b, c, d = ev["a_eval"], ev["b_eval"], ev["c_eval"], ev["d_eval"]
+    zw, qa = ev["perm_eval"], ev["q_arith_eval"]
+    zh = (xin - 1) % R
+    l1 = zh * pow(n * (xi - 1) % R, -1, R) % R
+    p3 = (a + beta * ev["left_sigma_eval"] + gamma) * (b + beta * ev["right_sigma_eval"] + gamma) \
+        * (c + beta * ev["out_sigma_eval"] + gamma) % R
+    n_xi = (ev["lin_poly_eval"] + _pi_at(_as_ints(public_inputs), xi, n, omega, zh) - alpha * p3 * (d + gamma) * zw
+            - alpha * alpha * l1) % R
+    t_eval = n_xi * pow(zh, -1, R) % R
+    zc = alpha
+    for w, kj in zip((a, b, c, d), (k.to_int() if isinstance(k, BlsScalar) else int(k) for k in DEFAULT_K)):
+        zc = zc * (w + beta * kj * xi + gamma) % R
+
+    out = {}
+
+    def put(point, ca, cb):
+        s = out.setdefault(point, [0, 0])
+        s[0] = (s[0] + ca) % R
+        s[1] = (s[1] + cb) % R
+
+    # F_xi: t, v r, then sigma_1..3, a, b, c, d, q_arith, q_c, q_l, q_r with v^2 ..; the second side carries -F
+    for j in range(4):
+        put(cm["t_%d_comm" % (j + 1)], 0, -pow(xin, j, R))
+    for coeff, point in ((qa * a * b, pre["q_m"]), (qa * a, pre["q_l"]), (qa * b, pre["q_r"]), (qa * c, pre["q_o"]), (qa * d, pre["q_4"]),
+                         (qa, pre["q_c"]), (zc + alpha * alpha * l1, cm["z_comm"]), (-alpha * beta * zw * p3, pre["fourth_sigma"])):
+        put(point, 0, -v * coeff)
+    value = (t_eval + v * ev["lin_poly_eval"]) % R
+    vi = v
+    for point, f in ((pre["left_sigma"], "left_sigma_eval"), (pre["right_sigma"], "right_sigma_eval"), (pre["out_sigma"], "out_sigma_eval"),
+                     (cm["a_comm"], "a_eval"), (cm["b_comm"], "b_eval"), (cm["c_comm"], "c_eval"), (cm["d_comm"], "d_eval"),
+                     (pre["q_arith"], "q_arith_eval"), (pre["q_c"], "q_c_eval"), (pre["q_l"], "q_l_eval"), (pre["q_r"], "q_r_eval")):
+        vi = vi * v % R
+        put(point, 0, -vi)
+        value = (value + vi * ev[f]) % R
+    # u F_xiw: z, a, b, d with v'^0..3
+    vj = u
+    for point, f in ((cm["z_comm"], "perm_eval"), (cm["a_comm"], "a_next_eval"), (cm["b_comm"], "b_next_eval"), (cm["d_comm"], "d_next_eval")):
+        put(point, 0, -vj)
+        value = (value + vj * ev[f]) % R
+        vj = vj * v2 % R
+    put(ok.g, 0, value)
+    put(cm["w_z_comm"], 1, -xi)
+    put(cm["w_zw_comm"], u, -u * xi * omega)
+    return out
+
+
+def _scalar_rows(values) -> list:
+    rows = []
+    for x in values:
+        rows.append([w - (1 << 64) if w >> 63 else w for w in BlsScalar.from_int(x % R).limbs()])
+    return rows
+
+
+def _msm2(engine, table: dict) -> list:
+    """the two sums of a {point: [a, b]} table: one pg_msm call with two scalar columns"""
+    pts = list(table)
+    cols = torch.tensor([_scalar_rows(table[p][0] for p in pts), _scalar_rows(table[p][1] for p in pts)], dtype=torch.int64,
+                        device=engine.device).view(2, len(pts), 4)
+    return engine.msm(points_tensor(pts, engine.device), cols)
+
+
+def _check(engine, ok, pairs) -> list:
+    """pairs: [(A, B)] -> [bool], one pg_pairing_check over all"""
+    pts = points_tensor([p for ab in pairs for p in ab], engine.device).view(len(pairs), 2, 12)
+    res = pairing_check(engine, pts, [ok.prepared_tau_h, ok.prepared_h])
+    return [bool(x) for x in res.cpu().tolist()]
+
+
+def verify(proof: Proof, vk: VerifierKey, ok, public_inputs=None, label=b"plonk") -> bool:
+    """True iff the proof verifies under the verifier key vk and the OpeningKey ok, for the public inputs {row: value} (rows of
+    the padded circuit; canonical integers or BlsScalars).  False -- never an exception -- for xi^n = 1, a commitment off the
+    curve or outside the order-r subgroup, and any proof whose pairing check fails."""
+    table = sides(proof, vk, ok, public_inputs, label)
+    if table is None:
+        return False
+    a, b = _msm2(ok.engine, table)
+    return _check(ok.engine, ok, [(a, b)])[0]
+
+
+def _broadcast(x, n):
+    return list(x) if isinstance(x, (list, tuple)) else [x] * n
+
+
+def verify_each(proofs, vks, ok, public_inputs, label=b"plonk") -> list:
+    """verify for every proof, as one pg_pairing_check of len(proofs) checks (the sides from one two-column MSM per proof).
+    vks / public_inputs / label: one per proof, or one for all."""
+    n = len(proofs)
+    vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
+    out, pairs, where = [False] * n, [], []
+    for i, proof in enumerate(proofs):
+        table = sides(proof, vks[i], ok, pis[i], labels[i])
+        if table is not None:
+            pairs.append(tuple(_msm2(ok.engine, table)))
+            where.append(i)
+    if pairs:
+        for i, good in zip(where, _check(ok.engine, ok, pairs)):
+            out[i] = good
+    return out
+
+
+def verify_batch(proofs, vks, ok, public_inputs, label=b"plonk") -> bool:
+    """True iff every proof verifies (up to 2^-128): the proofs' sides folded with random 128-bit weights into one two-column MSM
+    over all their points -- shared key commitments merged -- and ONE two-pair check.  An empty batch is True."""
+    n = len(proofs)
+    if n == 0:
+        return True
+    vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
+    folded = {}
+    for i, proof in enumerate(proofs):
+        table = sides(proof, vks[i], ok, pis[i], labels[i])
+        if table is None:
+            return False
+        rho = 1 if i == 0 else secrets.randbits(128) | 1
+        for point, (ca, cb) in table.items():
+            s = folded.setdefault(point, [0, 0])
+            s[0] = (s[0] + rho * ca) % R
+            s[1] = (s[1] + rho * cb) % R
+    a, b = _msm2(ok.engine, folded)
+    return _check(ok.engine, ok, [(a, b)])[0]
