@@ -606,6 +606,38 @@ pg_status pg_srs_setup(pg_engine *e, const pg_scalar *tau, const pg_g1_affine *b
  * NULL pointers with count > 0, or coordinates not reduced -> PG_ERR_INVALID_ARGUMENT. */
 pg_status pg_g1_to_compressed(const pg_g1_affine *in, uint64_t count, uint8_t *out);
 
+/* ---- G1 ingestion: decompression, membership and compression in batches ----------------------------
+ * What a commit key made elsewhere needs before it can be trusted: every 48-byte encoding decoded, every point shown to be on
+ * the curve and of order dividing r.  One status byte per point: */
+enum {
+    PG_G1_OK = 0,
+    PG_G1_BAD_ENCODING = 1,    /* the compressed bit clear, an identity encoding other than c0 00 .. 00, or x >= p */
+    PG_G1_NOT_ON_CURVE = 2,    /* x^3 + 4 has no square root (decompression) / y^2 != x^3 + 4 (check) */
+    PG_G1_NOT_IN_SUBGROUP = 3, /* on the curve, but r P != O */
+    PG_G1_NOT_REDUCED = 4      /* pg_g1_check: limbs at or above p (pg_msm refuses such points too) */
+};
+/* pg_g1_decompress: d_out[i] = the point of d_in[48 i .. 48 i + 47] (device, the encoding of pg_g1_to_compressed), for i < n:
+ * y = (x^3 + 4)^((p + 1) / 4) with the sign of bit 5; with check_subgroup != 0 also the membership test (the endomorphism
+ * test phi(P) = [-u^2] P, which implies r P = O).  d_status[i] (device, n bytes) is the point's PG_G1_* value; a point whose
+ * status is not PG_G1_OK is written as the identity, never as garbage.  *d_first_bad (device, one uint64) = the smallest i
+ * with d_status[i] != PG_G1_OK, n if there is none.  1 <= n <= 2^32; d_in and d_out 16-byte aligned, d_first_bad 8-byte.
+ * pg_g1_check: the same statuses for n points already in limbs (PG_G1_NOT_REDUCED, then the curve, then the subgroup; the
+ * identity (0, 0) is PG_G1_OK); writes no point.
+ * pg_g1_compress: d_out[48 i ...] = the encoding of d_points[i]; the points' limbs must be reduced (those of
+ * pg_g1_decompress, pg_msm and pg_srs_setup are), nothing is checked on the device.
+ * n out of range, a NULL or misaligned pointer, or an output overlapping an input or another output ->
+ * PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise the calls only enqueue.  One lane per point, about 541 Fq products
+ * to decode and 1 280 to test membership; they keep no device memory. */
+pg_status pg_g1_decompress(pg_engine *e, const uint8_t *d_in, uint64_t n, int check_subgroup, pg_g1_affine *d_out, uint8_t *d_status,
+                           uint64_t *d_first_bad, void *stream);
+pg_status pg_g1_check(pg_engine *e, const pg_g1_affine *d_points, uint64_t n, uint8_t *d_status, uint64_t *d_first_bad, void *stream);
+pg_status pg_g1_compress(pg_engine *e, const pg_g1_affine *d_points, uint64_t n, uint8_t *d_out, void *stream);
+/* pg_g1_from_compressed, pg_g1_check_host (host only): the same routines on the host, one point after the other, for `count`
+ * encodings / points; pg_g1_from_compressed always tests membership.  They need no GPU.  NULL pointers with count > 0 ->
+ * PG_ERR_INVALID_ARGUMENT; a bad point is reported in status[i], not by the return value. */
+pg_status pg_g1_from_compressed(const uint8_t *in, uint64_t count, pg_g1_affine *out, uint8_t *status);
+pg_status pg_g1_check_host(const pg_g1_affine *in, uint64_t count, uint8_t *status);
+
 /* ---- openings: the prover's round 5 ---------------------------------------------------------------
  * Both calls take n_cols (1..32) columns p_j = d_cols[j] of n coefficients each (device, Montgomery form, 1 <= n <= 2^32) as a
  * HOST array of device pointers, which may repeat (one column can carry two weights), and n_cols host weights mu[j]; f is

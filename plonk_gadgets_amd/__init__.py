@@ -7,6 +7,7 @@ from .scalar import BlsScalar, bits_count, num_bits_closest_power_of_two  # noqa
 from .engine import DEFAULT_COSET_GENERATOR, DEFAULT_K, Columns, Engine, Layout, NonExistingInverse, PgError, domain_generator  # noqa: F401
 from .g1 import CommitKey, G1Affine, PolynomialDegreeTooLarge  # noqa: F401
 from .g2 import G2Affine, OpeningKey, PreparedG2  # noqa: F401
+from .srs import PublicParameters  # noqa: F401
 from .proof import Proof  # noqa: F401
 from .verifier import VerifierKey, pairing_check, pairing_gt, verify, verify_batch, verify_each  # noqa: F401
 from .transcript import Transcript  # noqa: F401

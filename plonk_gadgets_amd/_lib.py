@@ -206,6 +206,11 @@ SIGNATURES = {
     "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_srs_setup": (C.c_int, [C.c_void_p, _P(Scalar), _P(G1AffineC), C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_g1_to_compressed": (C.c_int, [_P(G1AffineC), C.c_uint64, C.c_void_p]),
+    "pg_g1_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_g1_check": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_g1_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_g1_from_compressed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_g1_check_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_poly_open": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "pg_poly_combine": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -1617,3 +1617,4 @@ pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_c
 #include "capi_msm.inc"
 #include "capi_open.inc"
 #include "capi_pairing.inc"
+#include "capi_codec.inc"

@@ -651,6 +651,60 @@ class Engine:
             raise PgError(st, "pg_msm")
         return points_of(out)
 
+    # ---- G1 ingestion (pg_g1_decompress, pg_g1_check, pg_g1_compress) --------------------------------------------
+    def _g1_points(self, points: torch.Tensor) -> None:
+        if not (points.dim() == 2 and points.shape[1] == 12 and points.dtype == torch.int64 and points.device == self.device
+                and points.is_contiguous() and points.shape[0] > 0):
+            raise ValueError("points must be a contiguous, non-empty int64[n, 12] tensor on the engine's device")
+
+    def _g1_decompress_into(self, data: torch.Tensor, check_subgroup: bool, out: torch.Tensor):
+        """data uint8[48 n] on the device -> (status uint8[n], first_bad int64[1]); the points go to out int64[n, 12]"""
+        n = data.numel() // 48
+        status = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        first_bad = torch.empty((1,), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_g1_decompress(self._h, data.data_ptr(), n, 1 if check_subgroup else 0, out.data_ptr(), status.data_ptr(),
+                                        first_bad.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_g1_decompress")
+        return status, first_bad
+
+    def g1_decompress(self, data, check_subgroup: bool = True):
+        """48-byte encodings -> (points int64[n, 12], status uint8[n]) on the device (pg_g1_decompress).  data: bytes, or a
+        uint8 tensor of 48 n elements (any shape; a host tensor is uploaded).  status[i] is a PG_G1_* value (g1.G1_STATUS names
+        them); a point whose status is not 0 is the identity.  With check_subgroup the order-r membership test runs too."""
+        if isinstance(data, (bytes, bytearray, memoryview)):
+            data = torch.frombuffer(bytearray(data), dtype=torch.uint8)
+        if not (isinstance(data, torch.Tensor) and data.dtype == torch.uint8 and data.numel() and data.numel() % 48 == 0):
+            raise ValueError("data must be bytes or a uint8 tensor of 48 n > 0 elements")
+        data = data.to(self.device).contiguous().view(-1)
+        out = torch.empty((data.numel() // 48, 12), dtype=torch.int64, device=self.device)
+        status, _ = self._g1_decompress_into(data, check_subgroup, out)
+        return out, status
+
+    def _g1_check(self, points: torch.Tensor):
+        self._g1_points(points)
+        n = points.shape[0]
+        status = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        first_bad = torch.empty((1,), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_g1_check(self._h, points.data_ptr(), n, status.data_ptr(), first_bad.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_g1_check")
+        return status, first_bad
+
+    def g1_check(self, points: torch.Tensor) -> torch.Tensor:
+        """status uint8[n] of points int64[n, 12] (pg_g1_check): 0 for a point with reduced limbs, on the curve and of order
+        dividing r (the identity included), else the PG_G1_* value of the first test it fails"""
+        return self._g1_check(points)[0]
+
+    def g1_compress(self, points: torch.Tensor) -> torch.Tensor:
+        """points int64[n, 12] -> their encodings uint8[n, 48] on the device (pg_g1_compress)"""
+        self._g1_points(points)
+        out = torch.empty((points.shape[0], 48), dtype=torch.uint8, device=self.device)
+        st = self._lib.pg_g1_compress(self._h, points.data_ptr(), points.shape[0], out.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_g1_compress")
+        return out
+
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
         """(num_bits int32[batch], row_off int64[batch+1], var_off int64[batch+1]) for the *_plan calls"""

@@ -1,6 +1,7 @@
 """BLS12-381 G1 on the host side of the commitments: G1Affine (the ABI's pg_g1_affine), CommitKey (the powers tau^i G of an
-insecure development SRS, on the device) and PolynomialDegreeTooLarge.  The arithmetic runs in libplonk_gadgets_hip.so
-(pg_msm, pg_srs_setup, pg_g1_to_compressed); this module only converts."""
+insecure development SRS or of a key loaded from bytes, on the device) and PolynomialDegreeTooLarge.  The arithmetic runs in
+libplonk_gadgets_hip.so (pg_msm, pg_srs_setup, pg_g1_to_compressed, pg_g1_decompress, pg_g1_compress); this module only
+converts and moves bytes."""
 from __future__ import annotations
 
 import ctypes as C
@@ -14,6 +15,12 @@ _R = 1 << 384
 _MASK = (1 << 64) - 1
 _GX = 0x17f1d3a73197d7942695638c4fa9ac0fc3688c4f9774b905a14e3a3f171bac586c55e83ff97a1aeffb3af00adb22c6bb
 _GY = 0x08b3f481e3aaa0f1a09e30ed741d8ae4fcf5e095d5d00af600db18cb2c04b3edd03cc744a2888ae40caa232946c5e7e1
+
+
+# the per-point status bytes of pg_g1_decompress / pg_g1_check (include/plonk_gadgets_hip.h)
+G1_STATUS = ("PG_G1_OK", "PG_G1_BAD_ENCODING", "PG_G1_NOT_ON_CURVE", "PG_G1_NOT_IN_SUBGROUP", "PG_G1_NOT_REDUCED")
+# points per chunk when a key streams between a file and the device (48 MiB of encodings, 96 MiB of limbs)
+LOAD_CHUNK = 1 << 20
 
 
 class PolynomialDegreeTooLarge(ValueError):
@@ -147,6 +154,107 @@ class CommitKey:
         if degree > self.max_degree:
             raise PolynomialDegreeTooLarge(f"degree {degree} > the key's {self.max_degree}")
         return CommitKey(self.engine, self.powers[:degree + 1])
+
+    # ---- bytes: 48 per power, no header (dusk-plonk 0.8's CommitKey::to_var_bytes as recalled [DEP-RECALL]: the container's
+    # parity is unpinned, the point encoding is the standard one) ---------------------------------------------------------------
+    def _chunks(self, chunk: int):
+        """the key's encodings, `chunk` powers at a time, as host bytes"""
+        n = self.powers.shape[0]
+        for start in range(0, n, chunk):
+            yield self.engine.g1_compress(self.powers[start:start + chunk]).cpu().numpy().tobytes()
+
+    def to_bytes(self) -> bytes:
+        return b"".join(self._chunks(LOAD_CHUNK))
+
+    def save(self, path, chunk: int = LOAD_CHUNK) -> None:
+        with open(path, "wb") as f:
+            for part in self._chunks(chunk):
+                f.write(part)
+
+    @staticmethod
+    def _raise_bad(index: int, status: int):
+        raise ValueError(f"power {index} of the commit key is bad: {G1_STATUS[status]}")
+
+    @staticmethod
+    def _ingest(engine, n: int, fill, check: bool, chunk: int) -> "CommitKey":
+        """n powers, `chunk` at a time, through ONE pinned buffer and one device buffer on the current stream:
+        fill(start, count, dst) puts the encodings of powers [start, start + count) into dst, a writable uint8 view of the
+        pinned buffer.  What overlaps is the host's part with the device's: chunk k is fetched (a file read, a copy out of the
+        caller's bytes) while the device still decodes chunk k - 1.  The upload of chunk k is ordered behind that decode on the
+        stream; once it has completed the pinned buffer is free again and chunk k - 1's verdict is there to be read without
+        waiting for anything, and only then is the decode of chunk k enqueued: the device idles for the 48-byte-per-power
+        upload between two decodes, not for the fetch."""
+        chunk = max(1, min(chunk, n))
+        powers = torch.empty((n, 12), dtype=torch.int64, device=engine.device)
+        pinned = torch.empty((48 * chunk,), dtype=torch.uint8).pin_memory()
+        host = pinned.numpy()
+        staged = torch.empty((48 * chunk,), dtype=torch.uint8, device=engine.device)
+        uploaded = torch.cuda.Event()
+        stream = torch.cuda.current_stream(engine.device)
+        before = None  # (start, count, status, first_bad) of the chunk whose decode is in flight
+        for start in range(0, n, chunk):
+            count = min(chunk, n - start)
+            fill(start, count, host[:48 * count])
+            staged[:48 * count].copy_(pinned[:48 * count], non_blocking=True)
+            uploaded.record(stream)
+            uploaded.synchronize()
+            if before is not None:
+                CommitKey._settle(before)
+            status, first_bad = engine._g1_decompress_into(staged[:48 * count], check, powers[start:start + count])
+            before = (start, count, status, first_bad)
+        CommitKey._settle(before)
+        return CommitKey(engine, powers)
+
+    @staticmethod
+    def _settle(entry) -> None:
+        start, count, status, first_bad = entry
+        bad = int(first_bad.item())
+        if bad != count:
+            CommitKey._raise_bad(start + bad, int(status[bad].item()))
+
+    @staticmethod
+    def from_bytes(engine, data, check: bool = True, chunk: int = LOAD_CHUNK) -> "CommitKey":
+        """the key of an SRS made elsewhere, from bytes or any buffer of them (a memoryview slice is not copied before its
+        upload).  Every power is decoded on the device and, with `check`, tested for membership of the order-r subgroup;
+        ValueError names the first bad power and its status.  (That the powers ARE successive powers of the opening key's tau
+        is PublicParameters.is_consistent's to say.)"""
+        import numpy as np
+        view = memoryview(data).cast("B")
+        if len(view) == 0:
+            raise ValueError("an empty commit key")
+        if len(view) % 48:
+            raise ValueError(f"a commit key is 48 bytes per power; {len(view)} is no multiple of 48")
+        src = np.frombuffer(view, dtype=np.uint8)
+
+        def fill(start, count, dst):
+            dst[:] = src[48 * start:48 * (start + count)]
+        return CommitKey._ingest(engine, len(view) // 48, fill, check, chunk)
+
+    @staticmethod
+    def load(engine, path, max_degree: int | None = None, check: bool = True, chunk: int = LOAD_CHUNK, offset: int = 0) -> "CommitKey":
+        """from_bytes for a file (from byte `offset` on), streamed `chunk` powers at a time through a pinned buffer: one chunk is
+        read from the file while the device decodes the one before (_ingest).  With max_degree only the first max_degree + 1
+        powers are read (PolynomialDegreeTooLarge if the file holds fewer)."""
+        import os
+        size = os.path.getsize(path) - offset
+        if size <= 0:
+            raise ValueError("an empty commit key")
+        if size % 48:
+            raise ValueError(f"a commit key is 48 bytes per power; {size} is no multiple of 48")
+        n = size // 48
+        if max_degree is not None:
+            if max_degree < 0:
+                raise ValueError("max_degree must be >= 0")
+            if max_degree + 1 > n:
+                raise PolynomialDegreeTooLarge(f"degree {max_degree} > the file's {n - 1}")
+            n = max_degree + 1
+        with open(path, "rb") as f:
+            f.seek(offset)
+
+            def fill(start, count, dst):
+                if f.readinto(memoryview(dst)) != 48 * count:
+                    raise ValueError(f"{path}: short read")
+            return CommitKey._ingest(engine, n, fill, check, chunk)
 
     def commit(self, polys: torch.Tensor):
         """sum_i c_i tau^i base for a polynomial int64[n, 4] (-> one G1Affine) or several int64[c, n, 4] (-> a list), coefficients
