@@ -595,6 +595,23 @@ typedef struct pg_g1_affine { uint64_t x[6], y[6]; } pg_g1_affine;
  * again), 16 (2^15 + 1) x 192 bytes of buckets and ~1 MB of per-window sums: about 5.6 GiB at n = 2^28. */
 pg_status pg_msm(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_scalars, uint64_t n, uint64_t n_cols,
                  uint64_t col_stride, pg_g1_affine *d_out, void *stream);
+/* pg_msm_segmented: many independent small sums in one call:
+ *   d_out[s * n_cols + j] = sum_{seg_off[s] <= i < seg_off[s + 1]} s_j[i] P_i        for s < n_segs, j < n_cols,
+ * normalised affine points; an empty segment gives the identity (0, 0).  Bases, scalars, col_stride and alignment are as for
+ * pg_msm.  seg_off is a HOST array of n_segs + 1 offsets with seg_off[0] = 0, non-decreasing, seg_off[n_segs] = n; it is
+ * checked here and copied to the device (it is the caller's again when the call returns).  A bad seg_off, n = 0 with
+ * n_segs > 0, n_cols = 0, a stride below n, n x n_cols >= 2^31 (or n_segs x n_cols >= 2^31), a NULL or misaligned pointer, or
+ * d_out overlapping an input -> PG_ERR_INVALID_ARGUMENT with nothing launched; n_segs = 0 does nothing and is PG_OK;
+ * otherwise the call only enqueues.
+ * Every product s_j[i] P_i is a scalar multiplication on a lane of its own: 86 fixed windows of signed 3-bit digits over a
+ * table 2P, 3P, 4P in LDS (255 doublings and up to 86 complete additions: about 3 500 Fq products per point and column,
+ * whatever the scalar).  One wave per (segment, column) then sums the segment's products -- a segment of any length is
+ * correct, only short ones are fast: one large sum is pg_msm's -- and one pass normalises all the sums.  Device memory the
+ * engine keeps for it (grow-only): 192 bytes x n x n_cols of products, 192 bytes x n_segs x n_cols of sums, 8 (n_segs + 1)
+ * bytes of offsets (and as many of pinned host memory). */
+pg_status pg_msm_segmented(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_scalars, uint64_t n, uint64_t n_cols,
+                           uint64_t col_stride, const uint64_t *seg_off /* HOST, n_segs + 1 */, uint64_t n_segs,
+                           pg_g1_affine *d_out /* [n_segs][n_cols] */, void *stream);
 /* pg_srs_setup: d_out[i] = tau^i * base for i < n (1 <= n <= 2^32), base == NULL meaning the generator G.  This is
  * dusk-plonk's PublicParameters::setup `powers_of_g` with the secret tau chosen by the caller: INSECURE, for development
  * and tests only (whoever knows tau can forge proofs).  tau (host, Montgomery form) = 0 or not reduced, a base (host) that

@@ -204,6 +204,8 @@ SIGNATURES = {
                               _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_poly_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p]),
     "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_msm_segmented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(C.c_uint64), C.c_uint64,
+                                   C.c_void_p, C.c_void_p]),
     "pg_srs_setup": (C.c_int, [C.c_void_p, _P(Scalar), _P(G1AffineC), C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_g1_to_compressed": (C.c_int, [_P(G1AffineC), C.c_uint64, C.c_void_p]),
     "pg_g1_decompress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),

@@ -142,6 +142,13 @@ struct pg_engine {
     // scratch of pg_msm (sort keys, partial and bucket sums) and of pg_srs_setup (fixed-base tables, a chunk of points): grow-only
     uint4 *d_msm = nullptr, *d_srs = nullptr;
     uint64_t msm_units = 0, srs_units = 0;  // (16-byte units)
+    // scratch of pg_msm_segmented (grow-only): products, sums and segment offsets; the pinned buffer its offsets are staged in
+    uint4 *d_msm_small = nullptr;
+    uint64_t msm_small_units = 0;  // (16-byte units)
+    uint64_t *h_seg = nullptr;
+    uint64_t seg_cap = 0;
+    hipEvent_t ev_seg = nullptr;  // the last copy out of h_seg
+    bool seg_pending = false;
     // scratch of pg_poly_open (grow-only): its tile totals and carries
     uint4 *d_open = nullptr;
     uint64_t open_units = 0;  // (16-byte units)
@@ -592,6 +599,9 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->d_eval) (void)hipFree(e->d_eval);
     if (e->d_msm) (void)hipFree(e->d_msm);
     if (e->d_srs) (void)hipFree(e->d_srs);
+    if (e->d_msm_small) (void)hipFree(e->d_msm_small);
+    if (e->ev_seg) { (void)hipEventSynchronize(e->ev_seg); (void)hipEventDestroy(e->ev_seg); }
+    if (e->h_seg) (void)hipHostFree(e->h_seg);
     if (e->d_open) (void)hipFree(e->d_open);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
@@ -1615,6 +1625,7 @@ pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_c
 #include "capi_composer.inc"
 #include "capi_dist.inc"
 #include "capi_msm.inc"
+#include "capi_msm_small.inc"
 #include "capi_open.inc"
 #include "capi_pairing.inc"
 #include "capi_codec.inc"

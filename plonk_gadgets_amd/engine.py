@@ -651,6 +651,37 @@ class Engine:
             raise PgError(st, "pg_msm")
         return points_of(out)
 
+    def msm_segmented(self, bases: torch.Tensor, scalars: torch.Tensor, offsets) -> torch.Tensor:
+        """many small sums in one call (pg_msm_segmented): bases and scalars as for msm; offsets a Python sequence or a CPU
+        int64 tensor of n_segs + 1 non-decreasing row offsets from 0 to n -> int64[n_segs, c, 12] on the device, row [s, j] the
+        normalised sum of column j over the rows offsets[s] .. offsets[s + 1] - 1 ((0, 0) for an empty segment)"""
+        if not (bases.dim() == 2 and bases.shape[1] == 12 and bases.dtype == torch.int64 and bases.device == self.device
+                and bases.is_contiguous()):
+            raise ValueError("bases must be a contiguous int64[n, 12] tensor on the engine's device")
+        if not (self._rows(scalars) and scalars.dim() in (2, 3)):
+            raise ValueError("scalars must be int64[n, 4] or int64[c, n, 4] on the device with contiguous rows")
+        cols = scalars.shape[0] if scalars.dim() == 3 else 1
+        n = scalars.shape[-2]
+        if n != bases.shape[0]:
+            raise ValueError(f"{n} scalars per column for {bases.shape[0]} bases")
+        stride = scalars.stride(0) // 4 if scalars.dim() == 3 and cols > 1 else n
+        if scalars.dim() == 3 and cols > 1 and scalars.stride(0) % 4:
+            raise ValueError("the columns of scalars must start on whole rows")
+        if isinstance(offsets, torch.Tensor):
+            if not (offsets.dim() == 1 and offsets.dtype == torch.int64 and offsets.device.type == "cpu"):
+                raise ValueError("offsets must be a Python sequence or a one-dimensional CPU int64 tensor")
+            offsets = offsets.tolist()
+        offsets = [int(x) for x in offsets]
+        if not offsets or any(x < 0 for x in offsets):
+            raise ValueError("offsets must hold n_segs + 1 non-negative row offsets")
+        segs = len(offsets) - 1
+        out = torch.empty((segs, cols, 12), dtype=torch.int64, device=self.device)
+        st = self._lib.pg_msm_segmented(self._h, bases.data_ptr(), scalars.data_ptr(), n, cols, stride,
+                                        (C.c_uint64 * len(offsets))(*offsets), segs, out.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_msm_segmented")
+        return out
+
     # ---- G1 ingestion (pg_g1_decompress, pg_g1_check, pg_g1_compress) --------------------------------------------
     def _g1_points(self, points: torch.Tensor) -> None:
         if not (points.dim() == 2 and points.shape[1] == 12 and points.dtype == torch.int64 and points.device == self.device

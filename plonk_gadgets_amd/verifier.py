@@ -4,8 +4,8 @@ The algebra is dusk-plonk 0.8's Proof::verify [DEP-RECALL]: the transcript of pr
 t(xi) from N(xi) = t(xi) Z_H(xi), [r] from the key's commitments with the proof's q_arith(xi), the two KZG openings (at xi and
 xi omega) folded by the separation challenge u into ONE check
     e(W_xi + u W_xiw, [tau]_2) e(-(xi W_xi + u xi omega W_xiw + F - E g), [1]_2) = 1,   F = F_xi + u F_xiw,  E = E_xi + u E_xiw.
-Both G1 arguments are linear combinations of the same ~27 points: one Engine.msm call with two scalar columns gives both,
-then one pg_pairing_check of two pairs.  Everything a proof can get wrong makes verify return False; it never raises for it.
+Both G1 arguments are linear combinations of the same ~22 points: one Engine.msm_segmented call (one segment, two scalar
+columns) gives both, then one pg_pairing_check of two pairs.  Everything a proof can get wrong makes verify return False; it never raises for it.
 
 Subgroup: G1Affine.from_compressed tests the curve equation only, so every commitment of a proof is tested here for r P = O,
 by a Jacobian double-and-add over Python integers (about 4 ms per point, cached; the key's 15 commitments are tested once).
@@ -17,8 +17,8 @@ verify_batch folds the proofs' two sides with 128-bit weights drawn from `secret
 check e(A_i, [tau]_2) e(B_i, [1]_2) is not 1, the folded product is a non-zero polynomial of degree 1 in each weight over GT
 (a group of prime order r), so it is 1 with probability at most 2^-128.  Weights from the OS rather than from a transcript over
 all proofs: nothing then depends on every verifier hashing the same bytes in the same order, and a verifier has no reason to
-be deterministic.  verify_each runs one two-column MSM per proof (a segmented pass does not exist in pg_msm) and then one
-pg_pairing_check of len(proofs) checks: the call that names the bad proof."""
+be deterministic.  verify_each sums every proof's two sides in ONE pg_msm_segmented call (a segment per proof, DESIGN section
+3.15) whose output goes straight into one pg_pairing_check of len(proofs) checks: the call that names the bad proof."""
 from __future__ import annotations
 
 import ctypes as C
@@ -262,6 +262,24 @@ def _msm2(engine, table: dict) -> list:
     return engine.msm(points_tensor(pts, engine.device), cols)
 
 
+def _msm2_segmented(engine, tables) -> torch.Tensor:
+    """the two sums of every {point: [a, b]} table of `tables`: the points and both scalar columns of all of them in one upload,
+    ONE pg_msm_segmented call with a segment per table -> int64[len(tables), 2, 12] on the device, as pairing_check takes it"""
+    pts, ca, cb, offsets = [], [], [], [0]
+    for table in tables:
+        for p, (a, b) in table.items():
+            pts.append(p)
+            ca.append(a)
+            cb.append(b)
+        offsets.append(len(pts))
+    n = len(pts)
+    flat = [w - (1 << 64) if w >> 63 else w for p in pts for w in p.limbs]
+    for rows in (_scalar_rows(ca), _scalar_rows(cb)):
+        flat.extend(w for row in rows for w in row)
+    buf = torch.tensor(flat, dtype=torch.int64).to(engine.device)
+    return engine.msm_segmented(buf[:12 * n].view(n, 12), buf[12 * n:].view(2, n, 4), offsets)
+
+
 def _check(engine, ok, pairs) -> list:
     """pairs: [(A, B)] -> [bool], one pg_pairing_check over all"""
     pts = points_tensor([p for ab in pairs for p in ab], engine.device).view(len(pairs), 2, 12)
@@ -276,8 +294,10 @@ def verify(proof: Proof, vk: VerifierKey, ok, public_inputs=None, label=b"plonk"
     table = sides(proof, vk, ok, public_inputs, label)
     if table is None:
         return False
-    a, b = _msm2(ok.engine, table)
-    return _check(ok.engine, ok, [(a, b)])[0]
+    # one segment of pg_msm_segmented, not pg_msm: 14.2 ms instead of 50.5 for these 22 points (DESIGN section 3.15,
+    # profiles/r15_msm_segmented.json)
+    res = pairing_check(ok.engine, _msm2_segmented(ok.engine, [table]), [ok.prepared_tau_h, ok.prepared_h])
+    return bool(res.cpu().tolist()[0])
 
 
 def _broadcast(x, n):
@@ -285,19 +305,20 @@ def _broadcast(x, n):
 
 
 def verify_each(proofs, vks, ok, public_inputs, label=b"plonk") -> list:
-    """verify for every proof, as one pg_pairing_check of len(proofs) checks (the sides from one two-column MSM per proof).
-    vks / public_inputs / label: one per proof, or one for all."""
+    """verify for every proof: one pg_msm_segmented call (a segment per proof, two columns) and one pg_pairing_check of
+    len(proofs) checks on its output.  vks / public_inputs / label: one per proof, or one for all."""
     n = len(proofs)
     vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
-    out, pairs, where = [False] * n, [], []
+    out, tables, where = [False] * n, [], []
     for i, proof in enumerate(proofs):
         table = sides(proof, vks[i], ok, pis[i], labels[i])
         if table is not None:
-            pairs.append(tuple(_msm2(ok.engine, table)))
+            tables.append(table)
             where.append(i)
-    if pairs:
-        for i, good in zip(where, _check(ok.engine, ok, pairs)):
-            out[i] = good
+    if tables:
+        res = pairing_check(ok.engine, _msm2_segmented(ok.engine, tables), [ok.prepared_tau_h, ok.prepared_h])
+        for i, good in zip(where, res.cpu().tolist()):
+            out[i] = bool(good)
     return out
 
 

@@ -1,8 +1,11 @@
-"""Times the verifier and writes profiles/r13_verify_rate.json:
+"""Times the verifier (DESIGN sections 3.13 and 3.15) and writes profiles/r15_verify_rate.json (profiles/r13_verify_rate.json is the
+run of section 3.13, before pg_msm_segmented, and stays as it is):
   single   one verify of a range_check circuit's proof, split into transcript (the host side: subgroup tests, challenges, the
-           two columns of coefficients), MSM (the one two-column pg_msm) and pairing (one pg_pairing_check of 1 x 2)
+           two columns of coefficients), MSM (the one two-column pg_msm; beside it the same table as ONE segment of
+           pg_msm_segmented) and pairing (one pg_pairing_check of 1 x 2)
   batch    verify_batch and verify_each at --sizes proofs (default 2^6, 2^10, 2^14; copies of four circuits' proofs, so the
-           subgroup tests hit their cache after the first four: the host's share is reported apart)
+           subgroup tests hit their cache after the first four: the host's share is reported apart); up to --per-proof-max
+           proofs also verify_each as it was before pg_msm_segmented, one pg_msm per proof (verify_each_per_proof_msm_ms)
   pairing  pg_pairing_check alone at --checks n_checks (default 1, 2^10, 2^14, 2^16) of two pairs: ms, checks/s, and the
            cost model's Fq products per check (FQ_MUL_PER_CHECK) per second over the fq_mul ceiling
   ceiling  tools/fq_mul_bench.hip re-measured in the same run (built with hipcc if the binary is missing)
@@ -10,7 +13,7 @@
 Without --phase it is the driver: every phase runs as a child process of its own under its own time limit, in that order, and
 the driver stops at the first phase that fails or times out (nothing more is started on the GPU after a fault); phases that did
 not run stay "unmeasured" in the JSON.  With --phase NAME it runs that phase and prints its JSON.
-usage: python tools/verify_rate.py [--sizes 64,1024,16384] [--checks 1,1024,16384,65536] [--out profiles/r13_verify_rate.json]"""
+usage: python tools/verify_rate.py [--sizes 64,1024,16384] [--checks 1,1024,16384,65536] [--out profiles/r15_verify_rate.json]"""
 import argparse
 import json
 import os
@@ -77,14 +80,23 @@ def phase_single():
             V._valid_limbs.cache_clear()
         t_tr, table = wall(lambda: V.sides(proof, vk, ok, pi), sync)
         t_msm, ab = wall(lambda: V._msm2(eng, table), sync)
+        t_seg, seg = wall(lambda: V._msm2_segmented(eng, [table]), sync)
+        assert pg.g1.points_of(seg[0]) == list(ab)
         t_pair, good = wall(lambda: V._check(eng, ok, [tuple(ab)]), sync)
         assert good == [True]
-        rows.append({"subgroup_cache": "cold" if cold else "warm", "transcript_ms": t_tr, "msm_ms": t_msm, "pairing_ms": t_pair,
-                     "total_ms": t_tr + t_msm + t_pair, "msm_points": len(table)})
+        rows.append({"subgroup_cache": "cold" if cold else "warm", "transcript_ms": t_tr, "msm_ms": t_msm, "msm_segmented_ms": t_seg,
+                     "pairing_ms": t_pair, "total_ms": t_tr + t_msm + t_pair, "total_segmented_ms": t_tr + t_seg + t_pair,
+                     "msm_points": len(table)})
     return {"verify": rows}
 
 
-def phase_batch(sizes):
+def each_per_proof(V, proofs, vks, ok, pis):
+    """verify_each as it was before pg_msm_segmented: one two-column pg_msm per proof, then one pg_pairing_check"""
+    pairs = [tuple(V._msm2(ok.engine, V.sides(p, vk, ok, pi))) for p, vk, pi in zip(proofs, vks, pis)]
+    return V._check(ok.engine, ok, pairs)
+
+
+def phase_batch(sizes, per_proof_max):
     import torch
     import plonk_gadgets_amd as pg
     from plonk_gadgets_amd import verifier as V
@@ -105,6 +117,10 @@ def phase_batch(sizes):
         t_each, goods = wall(lambda: pg.verify_each(proofs, vks, ok, pis), sync)
         assert all(goods)
         row.update({"verify_each_ms": t_each, "verify_each_proofs_per_s": n / t_each * 1e3})
+        if n <= per_proof_max:
+            t_old, goods = wall(lambda: each_per_proof(V, proofs, vks, ok, pis), sync)
+            assert all(goods)
+            row["verify_each_per_proof_msm_ms"] = t_old
         rows.append(row)
     return {"batches": rows}
 
@@ -175,12 +191,13 @@ def main():
     ap.add_argument("--phase", choices=[p for p, _ in PHASES])
     ap.add_argument("--sizes", default="64,1024,16384")
     ap.add_argument("--checks", default="1,1024,16384,65536")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r13_verify_rate.json"))
+    ap.add_argument("--per-proof-max", type=int, default=1024)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "r15_verify_rate.json"))
     args = ap.parse_args()
     sizes = [int(x) for x in args.sizes.split(",") if x]
     checks = [int(x) for x in args.checks.split(",") if x]
     if args.phase:
-        fn = {"single": phase_single, "batch": lambda: phase_batch(sizes), "pairing": lambda: phase_pairing(checks),
+        fn = {"single": phase_single, "batch": lambda: phase_batch(sizes, args.per_proof_max), "pairing": lambda: phase_pairing(checks),
               "ceiling": phase_ceiling, "model": phase_model}[args.phase]
         print(json.dumps(fn()))
         return
@@ -188,7 +205,8 @@ def main():
               "fq_mul_ceiling_source": "profiles/r11_fq_mul_bench.txt"}
     result.update({p: "unmeasured" for p, _ in PHASES})
     for phase, limit in PHASES:
-        cmd = [sys.executable, os.path.abspath(__file__), "--phase", phase, "--sizes", args.sizes, "--checks", args.checks]
+        cmd = [sys.executable, os.path.abspath(__file__), "--phase", phase, "--sizes", args.sizes, "--checks", args.checks,
+               "--per-proof-max", str(args.per_proof_max)]
         try:
             p = subprocess.run(cmd, capture_output=True, text=True, timeout=limit)
         except subprocess.TimeoutExpired:
