@@ -655,6 +655,70 @@ pg_status pg_g1_compress(pg_engine *e, const pg_g1_affine *d_points, uint64_t n,
 pg_status pg_g1_from_compressed(const uint8_t *in, uint64_t count, pg_g1_affine *out, uint8_t *status);
 pg_status pg_g1_check_host(const pg_g1_affine *in, uint64_t count, uint8_t *status);
 
+/* ---- the verifier's sides from proof bytes, a batch at a time --------------------------------------
+ * What lies between a proof's 1040 bytes (11 commitments of 48 bytes, 16 evaluations of 32) and the input of
+ * pg_msm_segmented: the Fiat-Shamir transcript (Merlin over STROBE-128 over Keccak-f[1600]), the seven challenges, the
+ * verifier's scalar algebra and the table of coefficients -- one proof per lane.  The KZG check of a proof is
+ *     e(sum_k a_k P_k, [tau]_2) e(sum_k b_k P_k, [1]_2) = 1
+ * over a fixed table of PG_PLONK_SIDES_ROWS = 23 rows (P_k, a_k, b_k) per proof:
+ *    0..10  the proof's a, b, c, d, z, t_1, t_2, t_3, t_4, w_z, w_zw commitments
+ *   11..21  the key's q_m, q_l, q_r, q_o, q_4, q_c, q_arith, left_sigma, right_sigma, out_sigma, fourth_sigma
+ *       22  the generator g of the opening key
+ * Equal points are not merged: a point that stands in two rows carries two scalars, and the sums are the same.
+ *
+ * pg_plonk_key: what the routine needs of a (verifier key, transcript label) pair.  The transcript does not start from
+ * scratch: `state`, `pos`, `pos_begin`, `cur_flags` are the STROBE-128 state as it stands after the label, the circuit's domain
+ * separator and the key's 15 commitments (the host computes that once per key and label; every operation that follows
+ * begins afresh, so cur_flags is carried but not read).  pos <= 165, pos_begin <= 166, log2_n <= 32; omega is the generator
+ * of the 2^log2_n domain, in Montgomery form; the points are trusted (nothing tests them).  1392 bytes. */
+#define PG_PLONK_PROOF_BYTES 1040
+#define PG_PLONK_SIDES_ROWS 23
+typedef struct pg_plonk_key {
+    uint8_t state[200];
+    uint8_t pos, pos_begin, cur_flags, log2_n;
+    uint32_t reserved;
+    pg_scalar omega;
+    pg_g1_affine points[11]; /* q_m, q_l, q_r, q_o, q_4, q_c, q_arith, left_sigma, right_sigma, out_sigma, fourth_sigma */
+    pg_g1_affine g;
+} pg_plonk_key;
+/* One status byte and one `where` byte per proof.  The tests run in the order key, commitments, evaluations, public inputs,
+ * xi^n; the first that fails is reported.  1..4 are the PG_G1_* status of the first bad commitment (decoded with the
+ * membership test), `where` its index among the 11; otherwise: */
+enum {
+    PG_SIDES_OK = 0,
+    PG_SIDES_BAD_EVALUATION = 5,   /* an evaluation's 32 bytes are not below r; `where` is its index among the 16 */
+    PG_SIDES_XI_IN_DOMAIN = 6,     /* xi^n = 1: Z_H(xi) = 0, nothing to divide by */
+    PG_SIDES_BAD_PUBLIC_INPUT = 7, /* a public-input row >= n, or a value whose limbs are not below r */
+    PG_SIDES_BAD_KEY = 8           /* d_key_index[i] >= n_keys, or a key record with pos, pos_begin or log2_n out of range */
+};
+/* pg_plonk_sides: for proof i < n (d_proofs[1040 i ..], device, 16-byte aligned) under the key d_keys[d_key_index[i]]
+ * (d_key_index == NULL: key 0 for all) with the public inputs rows d_pi_rows[k], values d_pi_vals[k] (Montgomery form) for
+ * d_pi_off[i] <= k < d_pi_off[i + 1] (d_pi_off == NULL: none, and the two arrays are not read; else all three non-NULL).
+ * d_pi_off is on the device, so nothing can check it here: it MUST be non-decreasing, and d_pi_rows and d_pi_vals must hold
+ * d_pi_off[n] entries -- the kernel reads every k the offsets name, and an offset past the arrays is an out-of-bounds read (a
+ * decreasing pair reads nothing for that proof).  The call writes
+ *   d_bases[23 i + k] = P_k,   d_scalars[23 i + k] = a_k,   d_scalars[col_stride + 23 i + k] = b_k,
+ * the layout pg_msm_segmented takes with n_cols = 2 and seg_off[s] = 23 s, and d_status[i], d_where[i].  A rejected proof's
+ * 23 rows are identities and zeros, never garbage: its two sums are then the identity and its pairing check PASSES, so the
+ * verdict on proof i is  d_status[i] == PG_SIDES_OK  AND  the pairing check.  A key index >= n_keys is a per-proof rejection
+ * (PG_SIDES_BAD_KEY), not an argument error: the indices are on the device and the call only enqueues.
+ * e, a pointer NULL or misaligned (16 bytes for proofs, keys, bases, scalars and values, 8 for offsets and rows, 4 for key
+ * indices), n x 23 >= 2^31, n_keys = 0, col_stride < 23 n, an output overlapping another output or the proofs, keys, key
+ * indices or offsets -> PG_ERR_INVALID_ARGUMENT with nothing launched; n = 0 is PG_OK and does nothing.  Two launches: the
+ * 11 n commitments decoded one per lane (about 1 820 Fq products each), then one lane per proof: 14 or 15 permutations, 112 +
+ * log2 n products in Fr plus at most 2 log2 n + 4 per public input, one inversion.  Device memory the engine keeps for it (grow-only):
+ * 11 n bytes.
+ * pg_plonk_sides_host (host only): the same routine on the host, one proof after the other, every pointer a host pointer
+ * (8-byte aligned where its elements are words); needs no GPU. */
+pg_status pg_plonk_sides(pg_engine *e, const uint8_t *d_proofs /* n x 1040 bytes */, uint64_t n, const pg_plonk_key *d_keys,
+                         uint64_t n_keys, const uint32_t *d_key_index /* [n], NULL = all 0 */,
+                         const uint64_t *d_pi_off /* [n + 1], NULL = no public inputs */, const uint64_t *d_pi_rows,
+                         const pg_scalar *d_pi_vals, pg_g1_affine *d_bases /* [23 n] */, pg_scalar *d_scalars /* [2][col_stride] */,
+                         uint64_t col_stride, uint8_t *d_status, uint8_t *d_where, void *stream);
+pg_status pg_plonk_sides_host(const uint8_t *proofs, uint64_t n, const pg_plonk_key *keys, uint64_t n_keys, const uint32_t *key_index,
+                              const uint64_t *pi_off, const uint64_t *pi_rows, const pg_scalar *pi_vals, pg_g1_affine *bases,
+                              pg_scalar *scalars, uint64_t col_stride, uint8_t *status, uint8_t *where);
+
 /* ---- openings: the prover's round 5 ---------------------------------------------------------------
  * Both calls take n_cols (1..32) columns p_j = d_cols[j] of n coefficients each (device, Montgomery form, 1 <= n <= 2^32) as a
  * HOST array of device pointers, which may repeat (one column can carry two weights), and n_cols host weights mu[j]; f is

@@ -9,7 +9,7 @@ from .g1 import CommitKey, G1Affine, PolynomialDegreeTooLarge  # noqa: F401
 from .g2 import G2Affine, OpeningKey, PreparedG2  # noqa: F401
 from .srs import PublicParameters  # noqa: F401
 from .proof import Proof  # noqa: F401
-from .verifier import VerifierKey, pairing_check, pairing_gt, verify, verify_batch, verify_each  # noqa: F401
+from .verifier import VerifierKey, pairing_check, pairing_gt, verify, verify_batch, verify_each, verify_encoded  # noqa: F401
 from .transcript import Transcript  # noqa: F401
 from .composer import (AllocatedScalar, StandardComposer, Variable, conditionally_select_one,  # noqa: F401
                        conditionally_select_zero, is_non_zero, max_bound, maybe_equal, range_check,

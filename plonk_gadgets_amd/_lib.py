@@ -67,6 +67,12 @@ class G2AffineC(C.Structure):
     _fields_ = [("x", C.c_uint64 * 12), ("y", C.c_uint64 * 12)]
 
 
+class PlonkKeyC(C.Structure):
+    """pg_plonk_key: the transcript's seed, log2 n, omega, the 11 key points of the sides table and the generator"""
+    _fields_ = [("state", C.c_uint8 * 200), ("pos", C.c_uint8), ("pos_begin", C.c_uint8), ("cur_flags", C.c_uint8), ("log2_n", C.c_uint8),
+                ("reserved", C.c_uint32), ("omega", Scalar), ("points", G1AffineC * 11), ("g", G1AffineC)]
+
+
 # every symbol include/plonk_gadgets_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -213,6 +219,10 @@ SIGNATURES = {
     "pg_g1_compress": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_g1_from_compressed": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_g1_check_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p]),
+    "pg_plonk_sides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                 C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_plonk_sides_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_poly_open": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "pg_poly_combine": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

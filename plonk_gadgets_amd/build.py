@@ -14,7 +14,8 @@ HEADERS = ["experiment.hpp", "fr.hpp", "emit.hpp", "invert.hpp", "range_gadgets.
            "capi_composer.inc", "capi_dist.inc", "capi_msm.inc", "capi_open.inc",
            "fq2.hpp", "fq12.hpp", "g2.hpp", "pairing.hpp", "pairing_constants.inc", "capi_pairing.inc",
            "g1_codec.hpp", "capi_codec.inc",
-           "msm_small.hpp", "capi_msm_small.inc"]
+           "msm_small.hpp", "capi_msm_small.inc",
+           "plonk_sides.hpp", "capi_sides.inc"]
 
 
 def hipcc() -> str:

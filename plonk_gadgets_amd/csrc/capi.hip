@@ -152,6 +152,9 @@ struct pg_engine {
     // scratch of pg_poly_open (grow-only): its tile totals and carries
     uint4 *d_open = nullptr;
     uint64_t open_units = 0;  // (16-byte units)
+    // scratch of pg_plonk_sides (grow-only): the decode status of every commitment, 11 bytes a proof
+    uint4 *d_sides = nullptr;
+    uint64_t sides_units = 0;  // (16-byte units)
 };
 
 namespace {
@@ -603,6 +606,7 @@ void pg_engine_destroy(pg_engine *e) {
     if (e->ev_seg) { (void)hipEventSynchronize(e->ev_seg); (void)hipEventDestroy(e->ev_seg); }
     if (e->h_seg) (void)hipHostFree(e->h_seg);
     if (e->d_open) (void)hipFree(e->d_open);
+    if (e->d_sides) (void)hipFree(e->d_sides);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
@@ -1629,3 +1633,4 @@ pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_c
 #include "capi_open.inc"
 #include "capi_pairing.inc"
 #include "capi_codec.inc"
+#include "capi_sides.inc"

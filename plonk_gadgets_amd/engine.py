@@ -736,6 +736,51 @@ class Engine:
             raise PgError(st, "pg_g1_compress")
         return out
 
+    # ---- the verifier's sides from proof bytes (pg_plonk_sides) ------------------------------------------------------
+    def plonk_sides(self, proofs: torch.Tensor, keys: torch.Tensor, key_index: torch.Tensor | None = None,
+                    pi_off: torch.Tensor | None = None, pi_rows: torch.Tensor | None = None, pi_vals: torch.Tensor | None = None,
+                    col_stride: int | None = None):
+        """pg_plonk_sides, everything on the device: proofs uint8[n, 1040] (or flat), keys uint8[n_keys * 1392] (the records of
+        VerifierKey.record back to back), key_index int32[n] or None (key 0 for all), the public inputs as CSR arrays pi_off
+        int64[n + 1], pi_rows int64[k], pi_vals int64[k, 4] (Montgomery limbs) or None for none -> (bases int64[23 n, 12],
+        scalars int64[2, col_stride, 4], status uint8[n], where uint8[n]): what msm_segmented takes with the offsets 23 i.  The
+        verdict on proof i is status[i] == 0 AND its pairing check (a rejected proof's rows are identities and zeros)."""
+        from .verifier import PROOF_BYTES, SIDES_ROWS, VerifierKey
+
+        def ok(t, dtype, what):
+            if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous()):
+                raise ValueError(f"{what} must be a contiguous {dtype} tensor on the engine's device")
+        ok(proofs, torch.uint8, "proofs")
+        ok(keys, torch.uint8, "keys")
+        if proofs.numel() % PROOF_BYTES or keys.numel() % VerifierKey.RECORD_SIZE:
+            raise ValueError(f"proofs are {PROOF_BYTES} bytes each and key records {VerifierKey.RECORD_SIZE}")
+        n, n_keys = proofs.numel() // PROOF_BYTES, keys.numel() // VerifierKey.RECORD_SIZE
+        if key_index is not None:
+            ok(key_index, torch.int32, "key_index")
+            if key_index.numel() != n:
+                raise ValueError("key_index holds one index per proof")
+        if pi_off is not None and (pi_rows is None or pi_rows.numel() == 0):
+            pi_off = pi_rows = pi_vals = None  # (no proof has a public input: the call takes no arrays then)
+        if pi_off is not None:
+            ok(pi_off, torch.int64, "pi_off")
+            ok(pi_rows, torch.int64, "pi_rows")
+            ok(pi_vals, torch.int64, "pi_vals")
+            if pi_off.numel() != n + 1 or pi_vals.numel() != 4 * pi_rows.numel():
+                raise ValueError("pi_off holds n + 1 offsets, pi_vals four limbs per row of pi_rows")
+        rows = SIDES_ROWS * n
+        col_stride = rows if col_stride is None else int(col_stride)
+        bases = torch.empty((rows, 12), dtype=torch.int64, device=self.device)
+        scalars = torch.empty((2, col_stride, 4), dtype=torch.int64, device=self.device)
+        status = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        where = torch.empty((n,), dtype=torch.uint8, device=self.device)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        st = self._lib.pg_plonk_sides(self._h, proofs.data_ptr(), n, keys.data_ptr(), n_keys, ptr(key_index), ptr(pi_off), ptr(pi_rows),
+                                      ptr(pi_vals), bases.data_ptr(), scalars.data_ptr(), col_stride, status.data_ptr(),
+                                      where.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_plonk_sides")
+        return bases, scalars, status, where
+
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------
     def ragged_buffers(self, batch: int):
         """(num_bits int32[batch], row_off int64[batch+1], var_off int64[batch+1]) for the *_plan calls"""

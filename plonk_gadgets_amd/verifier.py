@@ -18,7 +18,11 @@ check e(A_i, [tau]_2) e(B_i, [1]_2) is not 1, the folded product is a non-zero p
 (a group of prime order r), so it is 1 with probability at most 2^-128.  Weights from the OS rather than from a transcript over
 all proofs: nothing then depends on every verifier hashing the same bytes in the same order, and a verifier has no reason to
 be deterministic.  verify_each sums every proof's two sides in ONE pg_msm_segmented call (a segment per proof, DESIGN section
-3.15) whose output goes straight into one pg_pairing_check of len(proofs) checks: the call that names the bad proof."""
+3.15) whose output goes straight into one pg_pairing_check of len(proofs) checks: the call that names the bad proof.
+
+verify_encoded is verify_each for proofs given as bytes with the host out of the loop: pg_plonk_sides decodes
+the commitments, replays the transcript from a per-key seed (VerifierKey.record) and writes every proof's fixed table of 23 rows on
+the device, which the same segmented MSM and pairing check consume; `sides` above is the model it is tested against."""
 from __future__ import annotations
 
 import ctypes as C
@@ -27,6 +31,7 @@ import secrets
 
 import torch
 
+from . import _lib
 from .engine import DEFAULT_K, PgError, domain_generator
 from .g1 import P, G1Affine, points_tensor
 from .proof import COMMITMENTS, EVALUATIONS, Proof
@@ -36,6 +41,12 @@ from .transcript import R, Transcript
 SELECTORS = ("q_m", "q_l", "q_r", "q_o", "q_c", "q_4", "q_arith", "q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
 SIGMAS = ("left_sigma", "right_sigma", "out_sigma", "fourth_sigma")
 MAX_PAIRS = 8
+# pg_plonk_sides: a proof's bytes, the rows of its table, the key commitments of rows 11..21 in their order
+PROOF_BYTES = Proof.SIZE
+SIDES_ROWS = 23
+SIDES_KEY_ROWS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "left_sigma", "right_sigma", "out_sigma", "fourth_sigma")
+SIDES_STATUS = ("PG_SIDES_OK", "PG_G1_BAD_ENCODING", "PG_G1_NOT_ON_CURVE", "PG_G1_NOT_IN_SUBGROUP", "PG_G1_NOT_REDUCED",
+                "PG_SIDES_BAD_EVALUATION", "PG_SIDES_XI_IN_DOMAIN", "PG_SIDES_BAD_PUBLIC_INPUT", "PG_SIDES_BAD_KEY")
 
 
 # ---- G1 membership ----------------------------------------------------------------------------------------------------------
@@ -123,6 +134,7 @@ class VerifierKey:
     [r] uses q_m, q_l, q_r, q_o, q_4, q_c and fourth_sigma; the xi opening left / right / out_sigma, q_arith, q_c, q_l, q_r."""
     NAMES = SELECTORS + SIGMAS
     SIZE = 8 + 48 * len(NAMES)
+    RECORD_SIZE = C.sizeof(_lib.PlonkKeyC)
 
     def __init__(self, n: int, commitments: dict):
         if n < 1 or n & (n - 1):
@@ -133,6 +145,30 @@ class VerifierKey:
         self.commitments = {k: commitments[k] for k in self.NAMES}
         # tested once, here: verify() trusts its key
         self.valid = all(g1_in_subgroup(c) for c in self.commitments.values())
+        self._seeds = {}
+
+    def record(self, ok, label=b"plonk") -> bytes:
+        """the bytes of one pg_plonk_key for this key, the generator of the opening key `ok` and the transcript label: the
+        STROBE state after the label, circuit_domain_sep(n) and the 15 commitments (computed once per label and kept), log2 n,
+        omega, the 11 key points of the sides table, ok.g"""
+        label = bytes(label)
+        seed = self._seeds.get(label)
+        if seed is None:
+            tr = Transcript(label)
+            tr.circuit_domain_sep(self.n)
+            for name in self.NAMES:
+                tr.append_commitment(name.encode(), self.commitments[name])
+            st = tr.strobe
+            seed = self._seeds[label] = (bytes(st.state), st.pos, st.pos_begin, st.cur_flags)
+        rec = _lib.PlonkKeyC()
+        C.memmove(rec.state, seed[0], 200)
+        rec.pos, rec.pos_begin, rec.cur_flags = seed[1:]
+        rec.log2_n = self.n.bit_length() - 1
+        rec.omega = domain_generator(rec.log2_n).c
+        for k, name in enumerate(SIDES_KEY_ROWS):
+            rec.points[k] = self.commitments[name].c
+        rec.g = ok.g.c
+        return bytes(rec)
 
     def to_bytes(self) -> bytes:
         return self.n.to_bytes(8, "little") + b"".join(self.commitments[k].to_compressed() for k in self.NAMES)
@@ -320,6 +356,105 @@ def verify_each(proofs, vks, ok, public_inputs, label=b"plonk") -> list:
         for i, good in zip(where, res.cpu().tolist()):
             out[i] = bool(good)
     return out
+
+
+def _proof_bytes(proofs):
+    """(n, a uint8 tensor of n x 1040 bytes -- on whatever device it was given -- or a bytes-like)"""
+    if isinstance(proofs, torch.Tensor):
+        if proofs.dtype != torch.uint8 or proofs.numel() % PROOF_BYTES:
+            raise ValueError(f"a tensor of proofs is uint8[n, {PROOF_BYTES}]")
+        return proofs.numel() // PROOF_BYTES, proofs.contiguous().view(-1)
+    if isinstance(proofs, (bytes, bytearray, memoryview)):
+        data = bytes(proofs)
+    else:
+        parts = []
+        for p in proofs:
+            try:
+                parts.append(p.to_bytes())
+            except (PgError, ValueError):  # limbs that have no encoding: all zeros decode to PG_G1_BAD_ENCODING
+                parts.append(bytes(PROOF_BYTES))
+        data = b"".join(parts)
+    if len(data) % PROOF_BYTES:
+        raise ValueError(f"{len(data)} bytes are not a whole number of {PROOF_BYTES}-byte proofs")
+    return len(data) // PROOF_BYTES, data
+
+
+def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_status=False):
+    """verify_each for a batch given as BYTES, the sides built on the device (pg_plonk_sides).
+    proofs: a bytes-like of n x 1040, a uint8[n, 1040] tensor on the host or the device, or a list of Proof (taken by their
+    to_bytes).  vks / public_inputs / label: one per proof, or one for all.  One upload of the inputs (proofs, the records of
+    the distinct (key, label) pairs, key indices and the public inputs as CSR arrays, in one buffer), one pg_plonk_sides, one
+    pg_msm_segmented over the uniform offsets 23 i (which stages its n + 1 offsets itself: a second, small copy inside that
+    call), one pg_pairing_check, (status == 0) & check on the device, one download -> [bool].  Never raises for a bad proof;
+    ValueError only for a wrong total length.
+    The answer is verify's, proof by proof, with one exception: a public-input row >= n.  sides / verify take omega^row for
+    any row (row n is row 0 to them) and may accept; here such a proof is rejected with PG_SIDES_BAD_PUBLIC_INPUT.
+    With return_status also the lists (status, where) of pg_plonk_sides (SIDES_STATUS names the values; a key that is not
+    valid gives PG_SIDES_BAD_KEY)."""
+    engine = ok.engine
+    n, data = _proof_bytes(proofs)
+    if n == 0:
+        return ([], [], []) if return_status else []
+    vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
+    table, records, key_index, bad_key = {}, [], [], []
+    for i in range(n):
+        k = (id(vks[i]), bytes(labels[i]))
+        if k not in table:
+            table[k] = len(records)
+            records.append(vks[i].record(ok, k[1]))
+        key_index.append(table[k])
+        if not vks[i].valid:
+            bad_key.append(i)
+    pi_off, pi_rows, pi_vals = [0], [], []
+    for pi in pis:
+        for row, val in _as_ints(pi).items():
+            pi_rows.append(row)
+            pi_vals.extend(BlsScalar.from_int(val % R).limbs())
+        pi_off.append(len(pi_rows))
+
+    # one host buffer, every section on a 16-byte boundary
+    sections, size = [], 0
+
+    def section(raw):
+        nonlocal size
+        raw = bytes(raw)
+        sections.append((size, raw))
+        size = (size + len(raw) + 15) // 16 * 16
+        return sections[-1][0], len(raw)
+    on_device = isinstance(data, torch.Tensor) and data.device == engine.device
+    at = {}
+    if not on_device:
+        at["proofs"] = section(bytes(data.cpu().numpy()) if isinstance(data, torch.Tensor) else data)
+    at["keys"] = section(b"".join(records))
+    at["index"] = section((C.c_uint32 * n)(*key_index))
+    if pi_rows:
+        at["off"] = section((C.c_uint64 * (n + 1))(*pi_off))
+        at["rows"] = section((C.c_uint64 * len(pi_rows))(*[r & ((1 << 64) - 1) for r in pi_rows]))
+        at["vals"] = section((C.c_uint64 * len(pi_vals))(*pi_vals))
+    host = bytearray(size)
+    for off, raw in sections:
+        host[off:off + len(raw)] = raw
+    dev = torch.frombuffer(host, dtype=torch.uint8).to(engine.device)
+
+    def view(name, dtype=torch.uint8):
+        if name not in at:
+            return None
+        off, length = at[name]
+        return dev[off:off + length].view(dtype)
+    d_proofs = data if on_device else view("proofs")
+    if d_proofs.data_ptr() % 16:
+        d_proofs = d_proofs.clone()
+    vals = view("vals", torch.int64)
+    bases, scalars, status, where = engine.plonk_sides(d_proofs, view("keys"), view("index", torch.int32), view("off", torch.int64),
+                                                       view("rows", torch.int64), vals.view(-1, 4) if vals is not None else None)
+    sums = engine.msm_segmented(bases, scalars, range(0, SIDES_ROWS * n + 1, SIDES_ROWS))
+    good = pairing_check(engine, sums, [ok.prepared_tau_h, ok.prepared_h])
+    verdict = ((status == 0) & (good != 0)).to(torch.uint8)
+    verdict, status, where = torch.stack([verdict, status, where]).cpu().tolist()
+    for i in bad_key:  # sides() trusts a key only if it is valid
+        verdict[i], status[i], where[i] = 0, SIDES_STATUS.index("PG_SIDES_BAD_KEY"), 0
+    out = [bool(x) for x in verdict]
+    return (out, status, where) if return_status else out
 
 
 def verify_batch(proofs, vks, ok, public_inputs, label=b"plonk") -> bool:
