@@ -28,6 +28,7 @@
 #include "permutation_product.hpp"
 #include "ntt.hpp"
 #include "quotient.hpp"
+#include "host_util.hpp"
 
 #ifndef PG_GRID_BLOCKS_PER_CU
 // more workgroups than can be resident: the dispatcher back-fills CUs as tiles finish (+6 % over a persistent
@@ -44,45 +45,6 @@
 
 namespace {
 
-thread_local std::string g_last_error;
-
-pg_status fail(pg_status s, const std::string &msg) {
-    g_last_error = msg;
-    return s;
-}
-
-#define PG_HIP_TRY(expr)                                                                \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess)                                                           \
-            return fail(PG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-#define PG_TRY(expr)                   \
-    do {                               \
-        pg_status _s = (expr);         \
-        if (_s != PG_OK) return _s;    \
-    } while (0)
-
-inline pg::Fr to_fr(const pg_scalar *s) {
-    pg::Fr f;
-    std::memcpy(f.l, s->l, sizeof f.l);
-    return f;
-}
-inline void from_fr(const pg::Fr &f, pg_scalar *out) { std::memcpy(out->l, f.l, sizeof f.l); }
-
-inline bool aligned(const void *p, size_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
-// a BlsScalar is always fully reduced; reject limbs >= q instead of computing garbage
-bool is_reduced(const pg::Fr &f) {
-    const uint64_t Q[4] = {PG_Q0, PG_Q1, PG_Q2, PG_Q3};
-    for (int i = 3; i >= 0; i--) {
-        if (f.l[i] < Q[i]) return true;
-        if (f.l[i] > Q[i]) return false;
-    }
-    return false;
-}
-
 pg_status check_columns(const pg_columns *c) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "columns is NULL");
     const void *sc[6] = {c->q_m, c->q_l, c->q_r, c->q_o, c->q_c, c->var_values};
@@ -94,34 +56,24 @@ pg_status check_columns(const pg_columns *c) {
     return PG_OK;
 }
 
-pg_status check_scalars(const void *p, const char *what) {
-    if (!p || !aligned(p, 16)) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " NULL or not 16-byte aligned");
-    return PG_OK;
-}
-pg_status check_u64s(const void *p, const char *what, bool nullable = false) {
-    if (!p && nullable) return PG_OK;
-    if (!p || !aligned(p, 8)) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " NULL or not 8-byte aligned");
-    return PG_OK;
-}
-
 }  // namespace
 
 struct pg_engine {
     int device = -1;
     int num_cus = 0;
     uint4 *d_pow2 = nullptr;  // mont(2^i), i < 256
-    // scratch of the ragged plans (grow-only): per-item counts, block sums, error counter
-    uint32_t *d_rows = nullptr, *d_vars = nullptr;
-    uint64_t *d_blk_rows = nullptr, *d_blk_vars = nullptr;
-    unsigned long long *d_blk_agg = nullptr;  // single-launch plans (emit.hpp, PlanScan): published block totals; [blocks] = blocks done
-    uint32_t *d_err_count = nullptr;
+    // Every Scratch below is grow-only and freed by its destructor (delete e, the engine's device current: pg_engine_destroy).
+    // scratch of the ragged plans: per-item counts (uint32_t), block sums (uint64_t), error counter (uint32_t)
+    Scratch d_rows, d_vars, d_blk_rows, d_blk_vars;
+    Scratch d_blk_agg;  // single-launch plans (emit.hpp, PlanScan): published block totals (unsigned long long); [blocks] = blocks done
+    Scratch d_err_count;
     uint64_t scratch_items = 0, scratch_blocks = 0;
     // totals of the last plan, written by async copies into pinned host memory (read after a synchronisation)
     using PlanResult = pg::PlanTotals;
     PlanResult *h_plan = nullptr;
-    // scratch of the inversions (grow-only): the pre-pass parks an element and its running product (64 B per element),
+    // scratch of the inversions: the pre-pass parks an element and its running product (64 B per element),
     // the fused mix one running product per item (32 B)
-    uint4 *d_prefix = nullptr;
+    Scratch d_prefix;
     uint64_t inv_elems = 0;
     // the pre-pass runs on its own stream beside the rows-only emit launch
     hipStream_t side = nullptr;
@@ -130,58 +82,46 @@ struct pg_engine {
     hipStream_t last_stream = nullptr;
     bool have_last = false;
     hipEvent_t ev_switch = nullptr;
-    // scratch of pg_sigma_evaluations / pg_permutation_product (grow-only): flags, omega tables, tile products, denominators
-    uint4 *d_pp = nullptr;
-    uint64_t pp_units = 0;  // (16-byte units)
-    // scratch of pg_ntt (grow-only): its omega and coset tables
-    uint4 *d_ntt = nullptr;
-    uint64_t ntt_units = 0;  // (16-byte units)
-    // scratch of pg_quotient (grow-only): its table of the chunk's points x; of pg_poly_evaluate: its power tables and partial sums
-    uint4 *d_quot = nullptr, *d_eval = nullptr;
-    uint64_t quot_units = 0, eval_units = 0;  // (16-byte units)
-    // scratch of pg_msm (sort keys, partial and bucket sums) and of pg_srs_setup (fixed-base tables, a chunk of points): grow-only
-    uint4 *d_msm = nullptr, *d_srs = nullptr;
-    uint64_t msm_units = 0, srs_units = 0;  // (16-byte units)
-    // scratch of pg_msm_segmented (grow-only): products, sums and segment offsets; the pinned buffer its offsets are staged in
-    uint4 *d_msm_small = nullptr;
-    uint64_t msm_small_units = 0;  // (16-byte units)
+    // scratch of pg_sigma_evaluations / pg_permutation_product: flags, omega tables, tile products, denominators
+    Scratch d_pp;
+    // scratch of pg_ntt: its omega and coset tables
+    Scratch d_ntt;
+    // scratch of pg_quotient: its table of the chunk's points x; of pg_poly_evaluate: its power tables and partial sums
+    Scratch d_quot, d_eval;
+    // scratch of pg_msm (sort keys, partial and bucket sums) and of pg_srs_setup (fixed-base tables, a chunk of points)
+    Scratch d_msm, d_srs;
+    // scratch of pg_msm_segmented: products, sums and segment offsets; the pinned buffer its offsets are staged in
+    Scratch d_msm_small;
     uint64_t *h_seg = nullptr;
     uint64_t seg_cap = 0;
     hipEvent_t ev_seg = nullptr;  // the last copy out of h_seg
     bool seg_pending = false;
-    // scratch of pg_poly_open (grow-only): its tile totals and carries
-    uint4 *d_open = nullptr;
-    uint64_t open_units = 0;  // (16-byte units)
-    // scratch of pg_plonk_sides (grow-only): the decode status of every commitment, 11 bytes a proof
-    uint4 *d_sides = nullptr;
-    uint64_t sides_units = 0;  // (16-byte units)
+    // scratch of pg_poly_open: its tile totals and carries
+    Scratch d_open;
+    // scratch of pg_plonk_sides: the decode status of every commitment, 11 bytes a proof
+    Scratch d_sides;
 };
 
 namespace {
 
 pg_status ensure_scratch(pg_engine *e, uint64_t batch) {
-    if (batch <= e->scratch_items && e->d_err_count) return PG_OK;
+    if (batch <= e->scratch_items && e->d_err_count.get()) return PG_OK;
     PG_HIP_TRY(hipSetDevice(e->device));
-    if (e->d_rows) { (void)hipFree(e->d_rows); e->d_rows = nullptr; }
-    if (e->d_vars) { (void)hipFree(e->d_vars); e->d_vars = nullptr; }
-    if (e->d_blk_rows) { (void)hipFree(e->d_blk_rows); e->d_blk_rows = nullptr; }
-    if (e->d_blk_vars) { (void)hipFree(e->d_blk_vars); e->d_blk_vars = nullptr; }
-    if (e->d_blk_agg) { (void)hipFree(e->d_blk_agg); e->d_blk_agg = nullptr; }
     e->scratch_items = 0;
     const uint64_t items = batch < 1024 ? 1024 : batch;
     // (the published words: one per block of a plan kernel, or per wave of the fused mix's planning launch -- at most 2048
     // of those up to 2 M items, one per 1024 items beyond)
     const uint64_t nblk = std::max<uint64_t>((items + pg::kScanBlock - 1) / pg::kScanBlock, 2048);
-    PG_HIP_TRY(hipMalloc(&e->d_rows, items * sizeof(uint32_t)));
-    PG_HIP_TRY(hipMalloc(&e->d_vars, items * sizeof(uint32_t)));
-    PG_HIP_TRY(hipMalloc(&e->d_blk_rows, nblk * sizeof(uint64_t)));
-    PG_HIP_TRY(hipMalloc(&e->d_blk_vars, nblk * sizeof(uint64_t)));
-    PG_HIP_TRY(hipMalloc(&e->d_blk_agg, (nblk + 1) * sizeof(unsigned long long)));
-    PG_HIP_TRY(hipMemset(e->d_blk_agg, 0, (nblk + 1) * sizeof(unsigned long long)));  // zero between launches: the plan kernels leave them so
+    PG_TRY(e->d_rows.reserve(items * sizeof(uint32_t)));
+    PG_TRY(e->d_vars.reserve(items * sizeof(uint32_t)));
+    PG_TRY(e->d_blk_rows.reserve(nblk * sizeof(uint64_t)));
+    PG_TRY(e->d_blk_vars.reserve(nblk * sizeof(uint64_t)));
+    PG_TRY(e->d_blk_agg.reserve((nblk + 1) * sizeof(unsigned long long)));
+    PG_HIP_TRY(hipMemset(e->d_blk_agg.get(), 0, (nblk + 1) * sizeof(unsigned long long)));  // zero between launches: the plan kernels leave them so
     e->scratch_blocks = nblk;
-    if (!e->d_err_count) {
-        PG_HIP_TRY(hipMalloc(&e->d_err_count, sizeof(uint32_t)));
-        PG_HIP_TRY(hipMemset(e->d_err_count, 0, sizeof(uint32_t)));  // zero between calls (see error_plan)
+    if (!e->d_err_count.get()) {
+        PG_TRY(e->d_err_count.reserve(sizeof(uint32_t)));
+        PG_HIP_TRY(hipMemset(e->d_err_count.get(), 0, sizeof(uint32_t)));  // zero between calls (see error_plan)
     }
     e->scratch_items = items;
     return PG_OK;
@@ -192,14 +132,14 @@ pg_status ensure_scratch(pg_engine *e, uint64_t batch) {
 pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_t *d_var_off, bool with_errs) {
     const uint64_t nblk = (batch + pg::kScanBlock - 1) / pg::kScanBlock;
     pg::PlanScan P{};
-    P.agg = e->d_blk_agg;
+    P.agg = e->d_blk_agg.as<unsigned long long>();
     P.blocks_cap = (uint32_t)e->scratch_blocks;
-    P.blk_rows = e->d_blk_rows;
-    P.blk_vars = e->d_blk_vars;
+    P.blk_rows = e->d_blk_rows.as<uint64_t>();
+    P.blk_vars = e->d_blk_vars.as<uint64_t>();
     P.row_off = d_row_off;
     P.var_off = d_var_off;
     P.host = e->h_plan;
-    P.err_count = with_errs ? e->d_err_count : nullptr;
+    P.err_count = with_errs ? e->d_err_count.as<uint32_t>() : nullptr;
 #if defined(PG_PLAN_TWO_LAUNCHES)  // A/B build
     P.fused = 0;
 #else
@@ -226,9 +166,11 @@ pg_status scan_counts(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_
     if (!plan_scan(e, batch, d_row_off, d_var_off, with_errs).fused) {
         const uint32_t prefixed = nblk > pg::kScanDirectBlocks ? 1u : 0u;
         if (prefixed)
-            hipLaunchKernelGGL(pg::scan_top_kernel, dim3(1), dim3(pg::kThreads), 0, st, e->d_blk_rows, e->d_blk_vars, nblk);
-        hipLaunchKernelGGL(pg::scan_final_kernel, dim3(nblk), dim3(pg::kThreads), 0, st, e->d_rows, e->d_vars, batch,
-                           e->d_blk_rows, e->d_blk_vars, d_row_off, d_var_off, prefixed, e->h_plan, with_errs ? e->d_err_count : nullptr);
+            hipLaunchKernelGGL(pg::scan_top_kernel, dim3(1), dim3(pg::kThreads), 0, st, e->d_blk_rows.as<uint64_t>(),
+                               e->d_blk_vars.as<uint64_t>(), nblk);
+        hipLaunchKernelGGL(pg::scan_final_kernel, dim3(nblk), dim3(pg::kThreads), 0, st, e->d_rows.as<uint32_t>(),
+                           e->d_vars.as<uint32_t>(), batch, e->d_blk_rows.as<uint64_t>(), e->d_blk_vars.as<uint64_t>(), d_row_off,
+                           d_var_off, prefixed, e->h_plan, with_errs ? e->d_err_count.as<uint32_t>() : nullptr);
         PG_HIP_TRY(hipGetLastError());
     }
     if (n_rows) {  // synchronous form
@@ -268,10 +210,9 @@ pg::EmitOut make_out(const pg_columns *c, uint64_t batch, int W, uint64_t gate_b
 pg_status ensure_inv_scratch(pg_engine *e, uint64_t elems) {
     if (elems <= e->inv_elems) return PG_OK;
     PG_HIP_TRY(hipSetDevice(e->device));
-    if (e->d_prefix) { (void)hipFree(e->d_prefix); e->d_prefix = nullptr; }
     e->inv_elems = 0;
     // per element: the element and its running product; + 64 x 16 bytes that the fused mix's masked lanes store to
-    PG_HIP_TRY(hipMalloc(&e->d_prefix, (elems * 4 + 64 + 4 * 32 * 32 * 8) * sizeof(uint4)));  // (+ the fused mix's last workgroup: whole steps of whole waves)
+    PG_TRY(e->d_prefix.reserve((elems * 4 + 64 + 4 * 32 * 32 * 8) * sizeof(uint4)));  // (+ the fused mix's last workgroup: whole steps of whole waves)
     e->inv_elems = elems;
     return PG_OK;
 }
@@ -361,13 +302,13 @@ pg_status launch_mix(pg_engine *e, const pg::ScalarMixArgs &A, const pg_columns 
     const uint32_t max_blocks = (uint32_t)e->num_cus * PG_GRID_BLOCKS_PER_CU;
     const dim3 grid(R.tiles < max_blocks ? R.tiles : max_blocks), vgrid((uint32_t)((waves + pg::kMixWaves - 1) / pg::kMixWaves));
     const dim3 vblock(pg::kMixWaves * 64);
-    uint4 *sink = e->d_prefix + e->inv_elems * 4 + 4 * 32 * 32 * 8;
+    uint4 *const prefix = e->d_prefix.as<uint4>(), *sink = prefix + e->inv_elems * 4 + 4 * 32 * 32 * 8;
     if (planned) {
         pg::MixPlan P = *planned;
         P.nwaves = vgrid.x;  // (the look-back is over workgroups)
-        hipLaunchKernelGGL(pg::scalar_mix_vars_kernel<true>, vgrid, vblock, 0, st, A, V, (uint32_t)ipl, e->d_prefix, sink, P);
+        hipLaunchKernelGGL(pg::scalar_mix_vars_kernel<true>, vgrid, vblock, 0, st, A, V, (uint32_t)ipl, prefix, sink, P);
     } else
-        hipLaunchKernelGGL(pg::scalar_mix_vars_kernel<false>, vgrid, vblock, 0, st, A, V, (uint32_t)ipl, e->d_prefix, sink,
+        hipLaunchKernelGGL(pg::scalar_mix_vars_kernel<false>, vgrid, vblock, 0, st, A, V, (uint32_t)ipl, prefix, sink,
                            pg::MixPlan{});
     if (values_only) {  // a witness refresh: the variable table (and, planned, the prefix sums) alone
         PG_HIP_TRY(hipGetLastError());
@@ -430,12 +371,12 @@ pg_status launch(pg_engine *e, const typename GD::Args &A, const pg_columns *c, 
                 inv_st = e->side;
             }
             if constexpr (pg::InvDense<GD>::ok) {
-                O.inv_dense = e->d_prefix;
+                O.inv_dense = e->d_prefix.as<uint4>();
                 O.inv_elems = elems;
                 O.inv_in_place = side;  // else the pre-pass is through before the emitter starts: it leaves the inverses where it computed them
             }
             hipLaunchKernelGGL((pg::batch_invert_kernel<GD, GRP>), dim3(blocks), dim3(pg::kThreads), 0, inv_st, A, O, elems,
-                               (uint32_t)groups, e->d_prefix);
+                               (uint32_t)groups, e->d_prefix.as<uint4>());
             PG_HIP_TRY(hipGetLastError());
             if (side) PG_HIP_TRY(hipEventRecord(e->ev_inv, e->side));
         }
@@ -478,7 +419,8 @@ pg_status error_plan_launch(pg_engine *e, PlanKernel kernel, const pg_scalar *d_
                             uint64_t *d_var_off, uint8_t *d_err_mask, hipStream_t st) {
     const uint32_t grid = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(pg::kThreads), 0, st, reinterpret_cast<const uint4 *>(d_value), batch,
-                       e->d_rows, e->d_vars, d_err_mask, e->d_err_count, plan_scan(e, batch, d_row_off, d_var_off, true));
+                       e->d_rows.as<uint32_t>(), e->d_vars.as<uint32_t>(), d_err_mask, e->d_err_count.as<uint32_t>(),
+                       plan_scan(e, batch, d_row_off, d_var_off, true));
     PG_HIP_TRY(hipGetLastError());
     return scan_counts(e, batch, d_row_off, d_var_off, nullptr, nullptr, st, true);
 }
@@ -507,7 +449,8 @@ pg_status error_plan(pg_engine *e, PlanKernel kernel, const pg_scalar *d_value, 
     // e->d_err_count is zero between calls: whoever reads it (scan_final_kernel, the bulk decoder) leaves it so
     const uint32_t grid = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(pg::kThreads), 0, st, reinterpret_cast<const uint4 *>(d_value), batch,
-                       e->d_rows, e->d_vars, d_err_mask, e->d_err_count, plan_scan(e, batch, d_row_off, d_var_off, true));
+                       e->d_rows.as<uint32_t>(), e->d_vars.as<uint32_t>(), d_err_mask, e->d_err_count.as<uint32_t>(),
+                       plan_scan(e, batch, d_row_off, d_var_off, true));
     PG_HIP_TRY(hipGetLastError());
     PG_TRY(scan_counts(e, batch, d_row_off, d_var_off, &out->n_gates, &out->n_vars, st, true));
     const uint32_t errs = e->h_plan->errs;
@@ -589,30 +532,14 @@ void pg_engine_destroy(pg_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->d_pow2) (void)hipFree(e->d_pow2);
-    if (e->d_rows) (void)hipFree(e->d_rows);
-    if (e->d_vars) (void)hipFree(e->d_vars);
-    if (e->d_blk_rows) (void)hipFree(e->d_blk_rows);
-    if (e->d_blk_vars) (void)hipFree(e->d_blk_vars);
-    if (e->d_err_count) (void)hipFree(e->d_err_count);
-    if (e->d_blk_agg) (void)hipFree(e->d_blk_agg);
-    if (e->d_prefix) (void)hipFree(e->d_prefix);
-    if (e->d_pp) (void)hipFree(e->d_pp);
-    if (e->d_ntt) (void)hipFree(e->d_ntt);
-    if (e->d_quot) (void)hipFree(e->d_quot);
-    if (e->d_eval) (void)hipFree(e->d_eval);
-    if (e->d_msm) (void)hipFree(e->d_msm);
-    if (e->d_srs) (void)hipFree(e->d_srs);
-    if (e->d_msm_small) (void)hipFree(e->d_msm_small);
     if (e->ev_seg) { (void)hipEventSynchronize(e->ev_seg); (void)hipEventDestroy(e->ev_seg); }
     if (e->h_seg) (void)hipHostFree(e->h_seg);
-    if (e->d_open) (void)hipFree(e->d_open);
-    if (e->d_sides) (void)hipFree(e->d_sides);
     if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
     if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
     if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
     if (e->ev_switch) (void)hipEventDestroy(e->ev_switch);
     if (e->h_plan) (void)hipHostFree(e->h_plan);
-    delete e;
+    delete e;  // (every Scratch)
 }
 
 pg_status pg_engine_sync(pg_engine *e, void *stream) {
@@ -632,12 +559,13 @@ pg_status pg_scalars_from_canonical_batch(pg_engine *e, const void *d_bytes, uin
     PG_TRY(ensure_scratch(e, 1));
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_HIP_TRY(hipSetDevice(e->device));
-    PG_HIP_TRY(hipMemsetAsync(e->d_err_count, 0, sizeof(uint32_t), st));
+    uint32_t *const d_errs = e->d_err_count.as<uint32_t>();
+    PG_HIP_TRY(hipMemsetAsync(d_errs, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(pg::from_canonical_kernel, dim3((uint32_t)((batch + pg::kThreads - 1) / pg::kThreads)), dim3(pg::kThreads), 0, st,
-                       static_cast<const uint4 *>(d_bytes), batch, reinterpret_cast<uint4 *>(d_out), d_bad_mask, e->d_err_count);
+                       static_cast<const uint4 *>(d_bytes), batch, reinterpret_cast<uint4 *>(d_out), d_bad_mask, d_errs);
     PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(&e->h_plan->errs, e->d_err_count, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
-    PG_HIP_TRY(hipMemsetAsync(e->d_err_count, 0, sizeof(uint32_t), st));  // zero between calls (see error_plan)
+    PG_HIP_TRY(hipMemcpyAsync(&e->h_plan->errs, d_errs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PG_HIP_TRY(hipMemsetAsync(d_errs, 0, sizeof(uint32_t), st));  // zero between calls (see error_plan)
     PG_HIP_TRY(hipStreamSynchronize(st));
     const uint32_t bad = e->h_plan->errs;
     if (bad_count) *bad_count = bad;
@@ -757,8 +685,8 @@ pg_status pg_range_check_structure_batch(pg_engine *e, const pg_scalar *min_rang
     A.pow2 = e->d_pow2;
     const pg::EmitOut O = make_out(&c, batch, pg::RangeCheckGD::W, gate_base, var_base, 0, nullptr, nullptr);
     const uint32_t max_blocks = (uint32_t)e->num_cus * PG_GRID_BLOCKS_PER_CU;
-    hipLaunchKernelGGL((pg::emit_kernel<pg::RangeCheckGD, pg::EMIT_STRUCTURE>), dim3(O.tiles < max_blocks ? O.tiles : max_blocks), dim3(pg::kThreads),
-                       0, static_cast<hipStream_t>(stream), A, O);
+    hipLaunchKernelGGL((pg::emit_kernel<pg::RangeCheckGD, pg::EMIT_STRUCTURE>), dim3(grid_cap(O.tiles, max_blocks)), dim3(pg::kThreads), 0,
+                       static_cast<hipStream_t>(stream), A, O);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }
@@ -890,8 +818,8 @@ static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_m
     StreamScope scope{e, st};
     const uint32_t grid = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
     hipLaunchKernelGGL(pg::max_bound_plan_kernel, dim3(grid), dim3(pg::kThreads), 0, st,
-                       reinterpret_cast<const uint4 *>(d_max_range), batch, e->d_pow2, d_num_bits, e->d_rows, e->d_vars,
-                       plan_scan(e, batch, d_row_off, d_var_off, false));
+                       reinterpret_cast<const uint4 *>(d_max_range), batch, e->d_pow2, d_num_bits, e->d_rows.as<uint32_t>(),
+                       e->d_vars.as<uint32_t>(), plan_scan(e, batch, d_row_off, d_var_off, false));
     PG_HIP_TRY(hipGetLastError());
     // a max_bound plan has no failing items: the scan writes errs = 0 with the totals, in stream order
     if (!out) return scan_counts(e, batch, d_row_off, d_var_off, nullptr, nullptr, st, false);
@@ -1089,7 +1017,7 @@ static pg_status scalar_mix_planned_common(pg_engine *e, const pg_scalar *d_v, c
     A.b = reinterpret_cast<const uint4 *>(d_b);
     A.result_vars = d_result_vars;
     pg::MixPlan P{};  // the call plans itself: the launch that inverts also makes the prefix sums (scalar_gadgets.hpp)
-    P.agg = e->d_blk_agg;
+    P.agg = e->d_blk_agg.as<unsigned long long>();
     P.cap = (uint32_t)e->scratch_blocks;
     P.row_off = d_row_off;
     P.var_off = d_var_off;
@@ -1157,7 +1085,7 @@ pg_status pg_fill_bytes(pg_engine *e, void *d_dst, uint64_t bytes, uint32_t stre
     uint64_t pieces = (bytes / 16 / streams + 65535) / 65536;
     const uint64_t cap = (uint64_t)e->num_cus * PG_GRID_BLOCKS_PER_CU;
     if (pieces < 1) pieces = 1;  // (fewer units than streams: the remainder loop of workgroup 0 writes them)
-    hipLaunchKernelGGL(pg::fill_kernel, dim3((uint32_t)(pieces < cap ? pieces : cap)), dim3(pg::kThreads), 0,
+    hipLaunchKernelGGL(pg::fill_kernel, dim3(grid_cap(pieces, cap)), dim3(pg::kThreads), 0,
                        static_cast<hipStream_t>(stream), static_cast<uint4 *>(d_dst), bytes / 16, streams, pattern);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
@@ -1179,7 +1107,7 @@ pg_status pg_fill_columns(pg_engine *e, const pg_columns *out, uint64_t n_gates,
     pg::EmitOut O = make_out(out, 0, 1, 0, 0, 0, nullptr, nullptr);
     O.tiles = (uint32_t)tiles;
     const uint64_t cap = (uint64_t)e->num_cus * PG_GRID_BLOCKS_PER_CU;
-    hipLaunchKernelGGL(pg::fill_columns_kernel, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(pg::kThreads), 0,
+    hipLaunchKernelGGL(pg::fill_columns_kernel, dim3(grid_cap(tiles, cap)), dim3(pg::kThreads), 0,
                        static_cast<hipStream_t>(stream), O, n_gates, n_vars, rows_per_tile, vars_per_tile, pattern);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
@@ -1199,16 +1127,16 @@ pg::Fr domain_generator(uint32_t log2_n) {
     return w;
 }
 
-pg_status check_field(const pg_scalar *s, const char *what) {
-    if (!s) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " is NULL");
-    if (!is_reduced(to_fr(s))) return fail(PG_ERR_INVALID_ARGUMENT, std::string(what) + " is not reduced below the modulus");
-    return PG_OK;
-}
+// the parts of e->d_pp beyond the domain's tables
+struct PpScratch {
+    uint32_t *flags;
+    uint4 *tile_prod, *tile_carry, *den;  // the product's own arrays (pg_sigma_evaluations has none: tiles = den_units = 0)
+};
 
-// the call's domain: padded_n a power of two <= 2^32; scratch laid out as flags (1 unit) | lo | hi | the product's own arrays
-// (`extra` units); the tables built with multipliers c[j] on `st`
-pg_status pp_prepare(pg_engine *e, uint64_t padded_n, const pg_scalar *omega, const pg::Fr c[4], uint64_t extra, hipStream_t st,
-                     pg::PpDomain &D, uint32_t *&flags, uint4 *&rest) {
+// the call's domain: padded_n a power of two <= 2^32; scratch laid out as flags (1 unit) | lo | hi | 2 tiles of tile products |
+// 2 tiles of carries | den_units of denominators (16-byte units); the tables built with multipliers c[j] on `st`
+pg_status pp_prepare(pg_engine *e, uint64_t padded_n, const pg_scalar *omega, const pg::Fr c[4], uint64_t tiles, uint64_t den_units,
+                     hipStream_t st, pg::PpDomain &D, PpScratch &W) {
     if (padded_n == 0 || (padded_n & (padded_n - 1)) || padded_n > (1ull << 32))
         return fail(PG_ERR_INVALID_ARGUMENT, "padded_n must be a power of two <= 2^32");
     PG_TRY(check_field(omega, "omega"));
@@ -1217,26 +1145,24 @@ pg_status pp_prepare(pg_engine *e, uint64_t padded_n, const pg_scalar *omega, co
     while ((1ull << D.m) < padded_n) D.m++;
     D.L = D.m < pg::kPpLoBitsMax ? D.m : pg::kPpLoBitsMax;
     D.H = padded_n >> D.L;
-    const uint64_t units = 1 + 2 * ((1ull << D.L) + 4 * D.H) + extra;
-    if (units > e->pp_units) {
-        if (e->d_pp) (void)hipFree(e->d_pp);
-        e->d_pp = nullptr;
-        e->pp_units = 0;
-        PG_HIP_TRY(hipMalloc(&e->d_pp, units * sizeof(uint4)));
-        e->pp_units = units;
-    }
-    flags = reinterpret_cast<uint32_t *>(e->d_pp);
-    uint4 *lo = e->d_pp + 1, *hi = lo + 2 * (1ull << D.L);
+    uint4 *lo, *hi;
+    PG_TRY(e->d_pp.carve(16, [&](Carve cv) {
+        W.flags = cv.take<uint32_t>(1);
+        lo = cv.take<uint4>(2 * (1ull << D.L));
+        hi = cv.take<uint4>(8 * D.H);
+        W.tile_prod = cv.take<uint4>(2 * tiles);
+        W.tile_carry = cv.take<uint4>(2 * tiles);
+        W.den = cv.take<uint4>(den_units);
+        return cv.bytes();
+    }));
     D.lo = lo;
     D.hi = hi;
-    rest = hi + 8 * D.H;
     pg::PpPowers P;
-    P.pw[0] = to_fr(omega);
-    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    fill_squares(P.pw, to_fr(omega));
     for (int j = 0; j < 4; j++) P.c[j] = c[j];
-    PG_HIP_TRY(hipMemsetAsync(flags, 0, sizeof(uint32_t), st));
+    PG_HIP_TRY(hipMemsetAsync(W.flags, 0, sizeof(uint32_t), st));
     const uint64_t entries = (1ull << D.L) + D.H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * 8;
-    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, D.L, D.H, 4u, lo, hi);
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(grid_cap(want, cap)), dim3(pg::kThreads), 0, st, P, D.L, D.H, 4u, lo, hi);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }
@@ -1278,13 +1204,12 @@ pg_status pg_sigma_evaluations(pg_engine *e, const uint64_t *d_sigma, uint64_t p
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     pg::PpDomain D;
-    uint32_t *flags;
-    uint4 *rest;
-    PG_TRY(pp_prepare(e, padded_n, omega, c, 0, st, D, flags, rest));
+    PpScratch W;
+    PG_TRY(pp_prepare(e, padded_n, omega, c, 0, 0, st, D, W));
     const uint64_t want = (4 * padded_n + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)e->num_cus * 32;
-    hipLaunchKernelGGL(pg::pp_sigma_eval_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, D, d_sigma,
-                       reinterpret_cast<uint4 *>(d_out), flags);
-    return pp_finish(e, flags, st);
+    hipLaunchKernelGGL(pg::pp_sigma_eval_kernel, dim3(grid_cap(want, cap)), dim3(pg::kThreads), 0, st, D, d_sigma,
+                       reinterpret_cast<uint4 *>(d_out), W.flags);
+    return pp_finish(e, W.flags, st);
 }
 
 pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scalar *const d_wire_values[4], uint64_t n_values,
@@ -1312,24 +1237,23 @@ pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scala
     StreamScope scope{e, st};
     const uint64_t tiles = (padded_n + pg::kPpTile - 1) / pg::kPpTile;
     // launch 1 loops over the tiles with the workgroups that fit at once (two per CU: 178 registers), each owning a slab of denominators
-    const uint64_t resident = (uint64_t)e->num_cus * 2, grid = tiles < resident ? tiles : resident;
-    uint32_t *flags;
-    uint4 *rest;
-    PG_TRY(pp_prepare(e, padded_n, omega, c, 4 * tiles + 2 * grid * pg::kPpTile, st, A.D, flags, rest));
+    const uint64_t grid = grid_cap(tiles, (uint64_t)e->num_cus * 2);
+    PpScratch W;
+    PG_TRY(pp_prepare(e, padded_n, omega, c, tiles, 2 * grid * pg::kPpTile, st, A.D, W));
     A.n_values = n_values;
     A.sigma = d_sigma;
     A.gamma = to_fr(gamma);
     A.z = reinterpret_cast<uint4 *>(d_z);
     A.wrap = reinterpret_cast<uint4 *>(d_wrap);
-    A.tile_prod = rest;
-    A.tile_carry = rest + 2 * tiles;
-    A.den = rest + 4 * tiles;
+    A.tile_prod = W.tile_prod;
+    A.tile_carry = W.tile_carry;
+    A.den = W.den;
     A.tiles = tiles;
-    A.flags = flags;
+    A.flags = W.flags;
     hipLaunchKernelGGL(pg::pp_ratio_kernel, dim3((uint32_t)grid), dim3(pg::kThreads), 0, st, A);
     hipLaunchKernelGGL(pg::pp_carry_kernel, dim3(1), dim3(pg::kThreads), 0, st, A);
     hipLaunchKernelGGL(pg::pp_scan_kernel, dim3((uint32_t)tiles), dim3(pg::kThreads), 0, st, A);
-    return pp_finish(e, flags, st);
+    return pp_finish(e, W.flags, st);
 }
 
 }  // extern "C"
@@ -1337,18 +1261,26 @@ pg_status pg_permutation_product(pg_engine *e, uint64_t padded_n, const pg_scala
 /* ---- NTTs over the scalar field (ntt.hpp) -------------------------------------------------------------------------------- */
 namespace {
 
-// the tables of base^x, x < 2^m, at `at` (2 (2^L + H) units), built on `st`: lo[e] = base^e, hi[h] = c base^(h 2^L)
-pg::NttTable ntt_table(const pg::Fr &base, const pg::Fr &c, uint32_t m, uint4 *at, int num_cus, hipStream_t st) {
+// room for the tables of base^x, x < 2^m: lo (2^L entries) | hi (H entries), two 16-byte units an entry
+struct NttTableAt {
+    uint4 *lo, *hi;
+    uint32_t L;
+};
+NttTableAt ntt_table_part(Carve &cv, uint32_t m) {
     const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
-    const uint64_t H = (1ull << m) >> L;
+    uint4 *lo = cv.take<uint4>(2 * (1ull << L));
+    return NttTableAt{lo, cv.take<uint4>(2 * ((1ull << m) >> L)), L};
+}
+
+// the tables built at `at` (of ntt_table_part, for the same m) on `st`: lo[e] = base^e, hi[h] = c base^(h 2^L)
+pg::NttTable ntt_table(const pg::Fr &base, const pg::Fr &c, uint32_t m, const NttTableAt &at, int num_cus, hipStream_t st) {
+    const uint64_t H = (1ull << m) >> at.L;
     pg::PpPowers P{};
-    P.pw[0] = base;
-    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    fill_squares(P.pw, base);
     P.c[0] = c;
-    const uint64_t entries = (1ull << L) + H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)num_cus * 8;
-    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3((uint32_t)(want < cap ? want : cap)), dim3(pg::kThreads), 0, st, P, L, H, 1u, at,
-                       at + 2 * (1ull << L));
-    return pg::NttTable{at, at + 2 * (1ull << L), L};
+    const uint64_t entries = (1ull << at.L) + H, want = (entries + pg::kThreads - 1) / pg::kThreads, cap = (uint64_t)num_cus * 8;
+    hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(grid_cap(want, cap)), dim3(pg::kThreads), 0, st, P, at.L, H, 1u, at.lo, at.hi);
+    return pg::NttTable{at.lo, at.hi, at.L};
 }
 
 // enqueue the transform of pg_ntt (its arguments checked, `st` entered) on the n_cols columns of `data`; src non-NULL: the columns
@@ -1356,25 +1288,22 @@ pg::NttTable ntt_table(const pg::Fr &base, const pg::Fr &c, uint32_t m, uint4 *a
 pg_status ntt_enqueue(pg_engine *e, uint4 *data, const uint4 *src, uint64_t n_cols, uint64_t col_stride, uint32_t m, bool coset,
                       bool inverse, const pg::Fr &w, const pg::Fr &g, hipStream_t st) {
     const uint64_t n = 1ull << m;
-    const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
-    const uint64_t per_table = 2 * ((1ull << L) + (n >> L)), units = per_table * (coset ? 2 : 1);
-    if (units > e->ntt_units) {
-        if (e->d_ntt) (void)hipFree(e->d_ntt);
-        e->d_ntt = nullptr;
-        e->ntt_units = 0;
-        PG_HIP_TRY(hipMalloc(&e->d_ntt, units * sizeof(uint4)));
-        e->ntt_units = units;
-    }
+    NttTableAt w_at{}, g_at{};
+    PG_TRY(e->d_ntt.carve(16, [&](Carve cv) {
+        w_at = ntt_table_part(cv, m);
+        if (coset) g_at = ntt_table_part(cv, m);
+        return cv.bytes();
+    }));
     const pg::Fr n_inv = pg::fr_invert_or_zero(pg::fr_from_u64(n));  // (n = 2^32 fits: fr_from_u64 takes the full 64 bits)
     pg::NttPass P{};
     P.data = data;
     P.n_cols = n_cols;
     P.stride = col_stride;
     P.m = m;
-    P.w = ntt_table(inverse ? pg::fr_invert_or_zero(w) : w, pg::fr_one(), m, e->d_ntt, e->num_cus, st);
+    P.w = ntt_table(inverse ? pg::fr_invert_or_zero(w) : w, pg::fr_one(), m, w_at, e->num_cus, st);
     pg::NttTable none{nullptr, nullptr, 0}, gt = none;
-    if (coset) gt = inverse ? ntt_table(pg::fr_invert_or_zero(g), n_inv, m, e->d_ntt + per_table, e->num_cus, st)
-                            : ntt_table(g, pg::fr_one(), m, e->d_ntt + per_table, e->num_cus, st);
+    if (coset) gt = inverse ? ntt_table(pg::fr_invert_or_zero(g), n_inv, m, g_at, e->num_cus, st)
+                            : ntt_table(g, pg::fr_one(), m, g_at, e->num_cus, st);
     P.scale = n_inv;
     P.use_scale = inverse && !coset;
     const uint64_t resident = (uint64_t)e->num_cus * 3;  // (48 KiB of LDS per pass workgroup: three per CU)
@@ -1388,7 +1317,7 @@ pg_status ntt_enqueue(pg_engine *e, uint4 *data, const uint4 *src, uint64_t n_co
         P.pre = first && coset && !inverse ? gt : none;
         P.post = P.natural && coset && inverse ? gt : none;
         const uint64_t tiles = n_cols << (m - k - cb);
-        hipLaunchKernelGGL(pg::ntt_pass_kernel, dim3((uint32_t)(tiles < resident ? tiles : resident)), dim3(pg::kThreads), 0, st, P);
+        hipLaunchKernelGGL(pg::ntt_pass_kernel, dim3(grid_cap(tiles, resident)), dim3(pg::kThreads), 0, st, P);
     };
     if (m <= pg::kNttTileBits) {
         pass(m, m, 0, true, true);
@@ -1406,7 +1335,7 @@ pg_status ntt_enqueue(pg_engine *e, uint4 *data, const uint4 *src, uint64_t n_co
         P.pre = none;
         P.post = coset && inverse ? gt : none;
         const uint64_t tiles = n_cols << (m - 2 * pg::kNttRevBits), cap = (uint64_t)e->num_cus * 2;  // (66 KiB of LDS: two per CU)
-        hipLaunchKernelGGL(pg::ntt_reverse_kernel, dim3((uint32_t)(tiles < cap ? tiles : cap)), dim3(pg::kThreads), 0, st, P);
+        hipLaunchKernelGGL(pg::ntt_reverse_kernel, dim3(grid_cap(tiles, cap)), dim3(pg::kThreads), 0, st, P);
     }
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
@@ -1424,9 +1353,7 @@ pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_
     if (kind > PG_NTT_COSET_INVERSE) return fail(PG_ERR_INVALID_ARGUMENT, "unknown kind");
     const uint32_t m = log2_n;
     const uint64_t n = 1ull << m;
-    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
-    if (n_cols && (n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
-        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    PG_TRY(check_strided_columns(n, n_cols, col_stride));
     PG_TRY(check_field(omega, "omega"));
     pg::Fr w = to_fr(omega), x = w;
     for (uint32_t i = 1; i < m; i++) x = pg::fr_mul(x, x);
@@ -1451,22 +1378,6 @@ pg_status pg_ntt(pg_engine *e, pg_scalar *d_data, uint64_t n_cols, uint64_t col_
 
 /* ---- the quotient polynomial and evaluations at a point (quotient.hpp) -------------------------------------------------- */
 namespace {
-
-// a grow-only engine buffer of at least `units` 16-byte units
-pg_status grow_units(uint4 *&buf, uint64_t &have, uint64_t units) {
-    if (units <= have) return PG_OK;
-    if (buf) (void)hipFree(buf);
-    buf = nullptr;
-    have = 0;
-    PG_HIP_TRY(hipMalloc(&buf, units * sizeof(uint4)));
-    have = units;
-    return PG_OK;
-}
-
-bool overlaps(const void *a, uint64_t a_bytes, const void *b, uint64_t b_bytes) {
-    const uintptr_t x = reinterpret_cast<uintptr_t>(a), y = reinterpret_cast<uintptr_t>(b);
-    return x < y + b_bytes && y < x + a_bytes;
-}
 
 pg::Fr fr_sqr_times(pg::Fr x, uint32_t times) {  // x^(2^times)
     for (uint32_t i = 0; i < times; i++) x = pg::fr_mul(x, x);
@@ -1522,8 +1433,11 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
-    const uint32_t L = m < pg::kNttTileBits ? m : pg::kNttTileBits;
-    PG_TRY(grow_units(e->d_quot, e->quot_units, 2 * ((1ull << L) + (n >> L))));
+    NttTableAt x_at{};  // the chunk's points x
+    PG_TRY(e->d_quot.carve(16, [&](Carve cv) {
+        x_at = ntt_table_part(cv, m);
+        return cv.bytes();
+    }));
     const pg::Fr omega = fr_sqr_times(zeta, 2), zeta_n = fr_sqr_times(zeta, m), g_n = fr_sqr_times(g, m);
     uint4 *T = reinterpret_cast<uint4 *>(d_t), *S = reinterpret_cast<uint4 *>(d_scratch);
     pg::QuotientChunk A{};
@@ -1544,7 +1458,7 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
         };
         const pg::Fr c_j = pg::fr_sub(pg::fr_mul(g_n, zeta_jn), pg::fr_one());  // x^n - 1 on the chunk
         A.t = T + 2 * j * n;
-        A.x = ntt_table(omega, g_j, m, e->d_quot, e->num_cus, st);
+        A.x = ntt_table(omega, g_j, m, x_at, e->num_cus, st);
         A.alpha2_c = pg::fr_mul(alpha2, c_j);
         A.c_inv = pg::fr_invert_or_zero(c_j);
         for (int i = 0; i < 5; i++) PG_TRY(fwd(i, (uint32_t)i));  // a, b, c, d, z: resident for the chunk
@@ -1584,42 +1498,41 @@ pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_c
     PG_TRY(check_scalars(d_out, "d_out"));
     PG_TRY(check_field(point, "point"));
     if (n == 0 || n > (1ull << 32)) return fail(PG_ERR_INVALID_ARGUMENT, "n must be in [1, 2^32]");
-    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
-    if (n_cols && (n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
-        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    PG_TRY(check_strided_columns(n, n_cols, col_stride));
     if (n_cols == 0) return PG_OK;
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     pg::PolyEval A{};
     A.segs = (n + pg::kEvalSeg - 1) / pg::kEvalSeg;
-    PG_TRY(grow_units(e->d_eval, e->eval_units, 2 * (257 + (n_cols + 1) * A.segs)));
-    uint4 *lane = e->d_eval, *seg_lo = lane + 2 * 256, *seg = seg_lo + 2;
+    uint4 *lane, *seg_lo, *seg;
+    PG_TRY(e->d_eval.carve(16, [&](Carve cv) {
+        lane = cv.take<uint4>(2 * 256);
+        seg_lo = cv.take<uint4>(2);  // ONE entry directly in front of seg: the second pp_tables launch writes its lo table of 2^0 entries here
+        seg = cv.take<uint4>(2 * A.segs);
+        A.partial = cv.take<uint4>(2 * n_cols * A.segs);
+        return cv.bytes();
+    }));
     A.c = reinterpret_cast<const uint4 *>(d_coeffs);
     A.n_cols = n_cols;
     A.stride = col_stride;
     A.n = n;
     A.x_lane = lane;
     A.x_seg = seg;
-    A.partial = seg + 2 * A.segs;
     A.out = reinterpret_cast<uint4 *>(d_out);
     const pg::Fr x = to_fr(point);
     A.x256 = fr_sqr_times(x, 8);
     // lane[t] = x^t (t < 256); seg[s] = x^(s kEvalSeg) (s < segs)
     pg::PpPowers P{};
-    P.pw[0] = x;
-    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    fill_squares(P.pw, x);
     P.c[0] = pg::fr_one();
     hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(1), dim3(pg::kThreads), 0, st, P, 8u, (uint64_t)0, 1u, lane, lane);
-    P.pw[0] = fr_sqr_times(x, 14);
     static_assert(pg::kEvalSeg == (1u << 14), "x^kEvalSeg");
-    for (int b = 1; b < 32; b++) P.pw[b] = pg::fr_mul(P.pw[b - 1], P.pw[b - 1]);
+    fill_squares(P.pw, fr_sqr_times(x, 14));
     hipLaunchKernelGGL(pg::pp_tables_kernel, dim3(grid_of(e, A.segs + 1, 8)), dim3(pg::kThreads), 0, st, P, 0u, A.segs, 1u, seg_lo, seg);
-    hipLaunchKernelGGL(pg::poly_eval_kernel, dim3((uint32_t)(n_cols * A.segs < (uint64_t)e->num_cus * 8 ? n_cols * A.segs
-                                                                                                         : (uint64_t)e->num_cus * 8)),
-                       dim3(pg::kThreads), 0, st, A);
-    hipLaunchKernelGGL(pg::poly_eval_reduce_kernel, dim3((uint32_t)(n_cols < (uint64_t)e->num_cus * 8 ? n_cols : (uint64_t)e->num_cus * 8)),
-                       dim3(pg::kThreads), 0, st, A);
+    const uint64_t cap = (uint64_t)e->num_cus * 8;
+    hipLaunchKernelGGL(pg::poly_eval_kernel, dim3(grid_cap(n_cols * A.segs, cap)), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::poly_eval_reduce_kernel, dim3(grid_cap(n_cols, cap)), dim3(pg::kThreads), 0, st, A);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }

@@ -12,10 +12,8 @@ struct pg_composer {
     std::vector<pg::FourthWire> fourth;
     // footprints of the batched calls (permutation.hpp) and the grow-only scratch of pg_composer_permutation
     std::vector<pg::PermSeg> segs;
-    void *perm_small = nullptr, *perm_big = nullptr, *val_ws = nullptr;  // val_ws: gathered assignments of batched calls
-    void *perm_pieces = nullptr;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
-    size_t perm_pieces_bytes = 0;
-    size_t perm_small_bytes = 0, perm_big_bytes = 0, val_ws_bytes = 0;
+    Scratch perm_small, perm_big, val_ws;  // val_ws: gathered assignments of batched calls
+    Scratch perm_pieces;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
     std::vector<void *> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
     uint64_t *h_total = nullptr;  // pinned
     uint64_t perm_last_sparse = 0;  // size of the sparse list the last permutation needed
@@ -767,13 +765,9 @@ void pg_composer_destroy(pg_composer *c) {
         if (S.h) (void)hipHostFree(S.h);
         if (S.ev) (void)hipEventDestroy(S.ev);
     }
-    if (c->perm_small) (void)hipFree(c->perm_small);
-    if (c->perm_big) (void)hipFree(c->perm_big);
-    if (c->val_ws) (void)hipFree(c->val_ws);
-    if (c->perm_pieces) (void)hipFree(c->perm_pieces);
     for (void *p : c->ragged) (void)hipFree(p);
     if (c->h_total) (void)hipHostFree(c->h_total);
-    delete c;
+    delete c;  // (every Scratch)
 }
 
 uint64_t pg_composer_circuit_size(const pg_composer *c) { return c ? c->n : 0; }
@@ -1130,7 +1124,7 @@ pg_status pg_is_non_zero(pg_composer *c, pg_variable var, const pg_scalar *value
     return pg_composer_poly_gate(c, var, inv, one_v, &one, &zero, &zero, &neg_one, &zero, nullptr);  // :84-94  var * inv - 1 = 0
 }
 
-static pg_status perm_reserve(pg_composer *c, void **buf, size_t *have, size_t bytes);
+static pg_status perm_reserve(pg_composer *c, Scratch &buf, size_t bytes);
 
 // every item of a batched call creates all of its V Variables itself on its own L rows: a segment for the permutation
 static void add_segment(pg_composer *c, uint64_t batch, uint64_t n_gates, uint64_t n_vars, uint64_t foreign_per_item = 0,
@@ -1275,8 +1269,8 @@ pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, uin
     PG_TRY(check_var_arrays(c, {d_a_var, d_b_var}, batch, &dg));
     PG_TRY(need(c, rows * batch, vars * batch));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, &c->val_ws, &c->val_ws_bytes, 2 * batch * 32));
-    uint4 *va = static_cast<uint4 *>(c->val_ws), *vb = va + 2 * batch;
+    PG_TRY(perm_reserve(c, c->val_ws, 2 * batch * 32));
+    uint4 *va = c->val_ws.as<uint4>(), *vb = va + 2 * batch;
     const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
     hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_a_var, c->cols.vars, batch, va);
@@ -1380,8 +1374,8 @@ pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var
     pg_composer::Sig dg;
     PG_TRY(check_var_arrays(c, {d_var}, batch, &dg));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, &c->val_ws, &c->val_ws_bytes, batch * 32));
-    uint4 *vals = static_cast<uint4 *>(c->val_ws);
+    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
+    uint4 *vals = c->val_ws.as<uint4>();
     const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
     hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_var, c->cols.vars, batch, vals);
@@ -1714,15 +1708,11 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
 #ifndef PG_PERM_LDS_PAD
 #define PG_PERM_LDS_PAD 0
 #endif
-static pg_status perm_reserve(pg_composer *c, void **buf, size_t *have, size_t bytes) {
-    if (bytes <= *have) return PG_OK;
+// grows one of the composer's buffers once the stream has drained: work in flight may still read what is there
+static pg_status perm_reserve(pg_composer *c, Scratch &buf, size_t bytes) {
+    if (bytes <= buf.size()) return PG_OK;
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (*buf) (void)hipFree(*buf);
-    *buf = nullptr;
-    *have = 0;
-    PG_HIP_TRY(hipMalloc(buf, bytes));
-    *have = bytes;
-    return PG_OK;
+    return buf.reserve(bytes);
 }
 
 pg_status pg_composer_permutation_reserve(pg_composer *c, uint64_t sparse_positions) {
@@ -1772,10 +1762,10 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
     }
     if (c->n > at) gaps.emplace_back(at, c->n);
     for (const auto &g : gaps) gap_rows += g.second - g.first;
-    const size_t seg_bytes = (segs.size() * sizeof(pg::PermSeg) + 255) / 256 * 256;
-    const size_t fw_bytes = (c->fourth.size() * sizeof(pg::FourthWire) + 255) / 256 * 256;
-    PG_TRY(perm_reserve(c, &c->perm_small, &c->perm_small_bytes, seg_bytes + fw_bytes + 256));
-    char *small = static_cast<char *>(c->perm_small);
+    const size_t seg_bytes = round256(segs.size() * sizeof(pg::PermSeg));
+    const size_t fw_bytes = round256(c->fourth.size() * sizeof(pg::FourthWire));
+    PG_TRY(perm_reserve(c, c->perm_small, seg_bytes + fw_bytes + 256));
+    char *small = c->perm_small.as<char>();
     pg::PermCtx X;
     X.C = c->cols; X.n = c->n; X.padded_n = padded_n; X.zero_var = c->zero_var;
     X.segs = reinterpret_cast<const pg::PermSeg *>(small); X.n_segs = (uint32_t)segs.size();
@@ -1809,8 +1799,8 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
         for (const pg::PermSeg &s : segs)
             if (needs_pieces(s)) total_pieces += pieces_of(s);
         if (total_pieces) {
-            PG_TRY(perm_reserve(c, &c->perm_pieces, &c->perm_pieces_bytes, total_pieces * sizeof(uint32_t)));
-            uint32_t *at_piece = static_cast<uint32_t *>(c->perm_pieces);
+            PG_TRY(perm_reserve(c, c->perm_pieces, total_pieces * sizeof(uint32_t)));
+            uint32_t *at_piece = c->perm_pieces.as<uint32_t>();
             for (pg::PermSeg &s : segs)
                 if (needs_pieces(s)) {
                     s.piece_item = at_piece;
@@ -1839,10 +1829,10 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
     for (int attempt = 0;; attempt++) {
         uint64_t *nul = nullptr;
         PG_HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp_bytes, nul, nul, (size_t)cap, 0u, pos_bits + var_bits, c->stream));
-        const size_t kb = (cap * 8 + 255) / 256 * 256;
-        PG_TRY(perm_reserve(c, &c->perm_big, &c->perm_big_bytes, 2 * kb + tmp_bytes + 256));
-        k0 = reinterpret_cast<uint64_t *>(c->perm_big);
-        k1 = reinterpret_cast<uint64_t *>(static_cast<char *>(c->perm_big) + kb);
+        const size_t kb = round256(cap * 8);
+        PG_TRY(perm_reserve(c, c->perm_big, 2 * kb + tmp_bytes + 256));
+        k0 = c->perm_big.as<uint64_t>();
+        k1 = reinterpret_cast<uint64_t *>(c->perm_big.as<char>() + kb);
         const pg::PermSparse Q{k0, d_count, cap};
         hipLaunchKernelGGL(pg::perm_count_init_kernel, dim3(1), dim3(1), 0, c->stream, d_count, reserved);
         for (const pg::PermSeg &s : segs) {
@@ -1907,7 +1897,7 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
         cap = nS;
     }
     if (nS) {
-        PG_HIP_TRY(rocprim::radix_sort_keys(static_cast<char *>(c->perm_big) + 2 * ((cap * 8 + 255) / 256 * 256), tmp_bytes, k0, k1,
+        PG_HIP_TRY(rocprim::radix_sort_keys(c->perm_big.as<char>() + 2 * round256(cap * 8), tmp_bytes, k0, k1,
                                             (size_t)nS, 0u, pos_bits + var_bits, c->stream));
         nS -= holes;  // (sorted to the end: reserved slots of ladder items whose witness is zero_var -- the zero chain has those positions)
     }

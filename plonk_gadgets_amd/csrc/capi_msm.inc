@@ -13,21 +13,6 @@ inline pg::G1A to_g1a(const pg_g1_affine *p) {
     return a;
 }
 
-// carves 256-byte-aligned pieces out of one workspace block
-struct Carve {
-    char *p;
-    template <typename T>
-    T *take(uint64_t count) {
-        T *r = reinterpret_cast<T *>(p);
-        p += (count * sizeof(T) + 255) / 256 * 256;
-        return r;
-    }
-};
-
-uint64_t round256(uint64_t b) { return (b + 255) / 256 * 256; }
-
-uint32_t grid_for_lanes(uint64_t lanes, uint32_t threads) { return (uint32_t)((lanes + threads - 1) / threads); }
-
 }  // namespace
 
 extern "C" {
@@ -39,9 +24,7 @@ pg_status pg_msm(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_s
     PG_TRY(check_scalars(d_scalars, "d_scalars"));
     PG_TRY(check_scalars(d_out, "d_out"));
     if (n == 0 || n >= (1ull << 31)) return fail(PG_ERR_INVALID_ARGUMENT, "n must be in [1, 2^31)");
-    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
-    if (n_cols && (n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
-        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    PG_TRY(check_strided_columns(n, n_cols, col_stride));
     if (n_cols == 0) return PG_OK;
     const uint64_t out_bytes = n_cols * sizeof(pg_g1_affine);
     if (overlaps(d_out, out_bytes, d_bases, n * sizeof(pg_g1_affine)) ||
@@ -59,20 +42,24 @@ pg_status pg_msm(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_s
     const uint64_t lanes0 = (n + pg::kMsmRun - 1) / pg::kMsmRun, partA = 2 * lanes0,
                    partB = 2 * ((partA + pg::kMsmRun - 1) / pg::kMsmRun);
     const uint64_t nbk = (uint64_t)pg::kMsmWindows * (pg::kMsmBuckets + 1), nseg = (uint64_t)pg::kMsmWindows * pg::kMsmSegs;
-    const uint64_t bytes = 2 * round256(n * 8) + round256(sort_bytes) + round256(partA * 4) + round256(partA * sizeof(pg::G1X)) +
-                           round256(partB * 4) + round256(partB * sizeof(pg::G1X)) + round256(nbk * sizeof(pg::G1X)) +
-                           round256(nseg * sizeof(pg::G1X)) + round256(pg::kMsmWindows * sizeof(pg::G1X)) +
-                           round256(n_cols * sizeof(pg::G1X));
-    PG_TRY(grow_units(e->d_msm, e->msm_units, bytes / 16));
-    Carve cv{reinterpret_cast<char *>(e->d_msm)};
-    uint64_t *k0 = cv.take<uint64_t>(n), *k1 = cv.take<uint64_t>(n);
-    void *sort_tmp = cv.take<char>(sort_bytes);
-    uint32_t *pkA = cv.take<uint32_t>(partA);
-    pg::G1X *ppA = cv.take<pg::G1X>(partA);
-    uint32_t *pkB = cv.take<uint32_t>(partB);
-    pg::G1X *ppB = cv.take<pg::G1X>(partB);
-    pg::G1X *buckets = cv.take<pg::G1X>(nbk), *seg = cv.take<pg::G1X>(nseg), *win = cv.take<pg::G1X>(pg::kMsmWindows),
-            *res = cv.take<pg::G1X>(n_cols);
+    uint64_t *k0, *k1;
+    void *sort_tmp;
+    uint32_t *pkA, *pkB;
+    pg::G1X *ppA, *ppB, *buckets, *seg, *win, *res;
+    PG_TRY(e->d_msm.carve(256, [&](Carve cv) {
+        k0 = cv.take<uint64_t>(n);
+        k1 = cv.take<uint64_t>(n);
+        sort_tmp = cv.take<char>(sort_bytes);
+        pkA = cv.take<uint32_t>(partA);
+        ppA = cv.take<pg::G1X>(partA);
+        pkB = cv.take<uint32_t>(partB);
+        ppB = cv.take<pg::G1X>(partB);
+        buckets = cv.take<pg::G1X>(nbk);
+        seg = cv.take<pg::G1X>(nseg);
+        win = cv.take<pg::G1X>(pg::kMsmWindows);
+        res = cv.take<pg::G1X>(n_cols);
+        return cv.bytes();
+    }));
     const pg::G1A *bases = reinterpret_cast<const pg::G1A *>(d_bases);
     const uint32_t dgrid = grid_of(e, n, 8);
     for (uint64_t j = 0; j < n_cols; j++) {
@@ -123,18 +110,19 @@ pg_status pg_srs_setup(pg_engine *e, const pg_scalar *tau, const pg_g1_affine *b
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     const uint64_t chunk = n < pg::kSrsChunk ? n : pg::kSrsChunk;
-    const uint64_t bytes = round256(8192 * sizeof(pg::G1X)) + round256(8192 * sizeof(pg::G1A)) + round256(chunk * sizeof(pg::G1X));
-    PG_TRY(grow_units(e->d_srs, e->srs_units, bytes / 16));
-    Carve cv{reinterpret_cast<char *>(e->d_srs)};
-    pg::G1X *tx = cv.take<pg::G1X>(8192);
-    pg::G1A *ta = cv.take<pg::G1A>(8192);
-    pg::G1X *pts = cv.take<pg::G1X>(chunk);
+    pg::G1X *tx, *pts;
+    pg::G1A *ta;
+    PG_TRY(e->d_srs.carve(256, [&](Carve cv) {
+        tx = cv.take<pg::G1X>(8192);
+        ta = cv.take<pg::G1A>(8192);
+        pts = cv.take<pg::G1X>(chunk);
+        return cv.bytes();
+    }));
     hipLaunchKernelGGL(pg::srs_table_kernel, dim3(8192 / pg::kThreads), dim3(pg::kThreads), 0, st, b, tx);
     hipLaunchKernelGGL(pg::g1_normalize_kernel, dim3(grid_for_lanes(8192 / pg::kNormPerLane, pg::kThreads)), dim3(pg::kThreads), 0, st,
                        tx, ta, (uint64_t)8192, pg::kNormPerLane);
     pg::FrPow2 P{};
-    P.pw[0] = t;
-    for (int i = 1; i < 32; i++) P.pw[i] = pg::fr_mul(P.pw[i - 1], P.pw[i - 1]);
+    fill_squares(P.pw, t);
     pg::G1A *out = reinterpret_cast<pg::G1A *>(d_out);
     for (uint64_t start = 0; start < n; start += chunk) {
         const uint64_t count = n - start < chunk ? n - start : chunk;

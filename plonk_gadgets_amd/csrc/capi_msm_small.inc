@@ -1,5 +1,5 @@
-// capi_msm_small.inc -- pg_msm_segmented, included at the end of capi.hip after capi_msm.inc (its Carve, round256 and
-// grid_for_lanes): host-side validation, workspace and the launches of msm_small.hpp.  DESIGN section 3.15.
+// capi_msm_small.inc -- pg_msm_segmented, included at the end of capi.hip: host-side validation, workspace and the launches of
+// msm_small.hpp.  DESIGN section 3.15.
 #include "emit.hpp"  // kThreads
 #include "msm.hpp"   // g1_normalize_kernel, kNormPerLane
 #include "msm_small.hpp"
@@ -47,9 +47,7 @@ pg_status pg_msm_segmented(pg_engine *e, const pg_g1_affine *d_bases, const pg_s
         return fail(PG_ERR_INVALID_ARGUMENT, "n x n_cols must be below 2^31");
     if (n_segs >= (1ull << 31) || n_segs * n_cols >= (1ull << 31))
         return fail(PG_ERR_INVALID_ARGUMENT, "n_segs x n_cols must be below 2^31");
-    if (col_stride < n) return fail(PG_ERR_INVALID_ARGUMENT, "col_stride < n");
-    if ((n_cols - 1) > (UINT64_MAX / sizeof(pg_scalar) - n) / col_stride)
-        return fail(PG_ERR_INVALID_ARGUMENT, "n_cols x col_stride overflows the address space");
+    PG_TRY(check_strided_columns(n, n_cols, col_stride));
     if (seg_off[0] != 0 || seg_off[n_segs] != n) return fail(PG_ERR_INVALID_ARGUMENT, "seg_off must start at 0 and end at n");
     for (uint64_t k = 0; k < n_segs; k++)
         if (seg_off[k] > seg_off[k + 1]) return fail(PG_ERR_INVALID_ARGUMENT, "seg_off decreases");
@@ -61,17 +59,20 @@ pg_status pg_msm_segmented(pg_engine *e, const pg_g1_affine *d_bases, const pg_s
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     // workspace: the products, the segments' sums (both XYZZ) and the offsets
-    const uint64_t bytes = round256(lanes * sizeof(pg::G1X)) + round256(sums * sizeof(pg::G1X)) + round256((n_segs + 1) * 8);
-    PG_TRY(grow_units(e->d_msm_small, e->msm_small_units, bytes / 16));
-    Carve cv{reinterpret_cast<char *>(e->d_msm_small)};
-    pg::G1X *prod = cv.take<pg::G1X>(lanes), *res = cv.take<pg::G1X>(sums);
-    uint64_t *d_off = cv.take<uint64_t>(n_segs + 1);
+    pg::G1X *prod, *res;
+    uint64_t *d_off;
+    PG_TRY(e->d_msm_small.carve(256, [&](Carve cv) {
+        prod = cv.take<pg::G1X>(lanes);
+        res = cv.take<pg::G1X>(sums);
+        d_off = cv.take<uint64_t>(n_segs + 1);
+        return cv.bytes();
+    }));
     PG_TRY(stage_offsets(e, seg_off, n_segs + 1, d_off, st));
     hipLaunchKernelGGL(pg::msm_seg_mul_kernel, dim3(grid_for_lanes(lanes, pg::kSmallLanes)), dim3(pg::kSmallLanes), 0, st,
                        reinterpret_cast<const pg::G1A *>(d_bases), reinterpret_cast<const pg::Fr *>(d_scalars), n, n_cols, col_stride,
                        prod);
     const uint64_t sum_cap = (uint64_t)e->num_cus * 32;  // waves of the sums resident at once, about; the kernel walks the rest
-    hipLaunchKernelGGL(pg::msm_seg_sum_kernel, dim3((uint32_t)(sums < sum_cap ? sums : sum_cap)), dim3(pg::kSmallLanes), 0, st, prod,
+    hipLaunchKernelGGL(pg::msm_seg_sum_kernel, dim3(grid_cap(sums, sum_cap)), dim3(pg::kSmallLanes), 0, st, prod,
                        d_off, n, n_segs, n_cols, res);
     // one inversion per lane: a lane takes up to kNormPerLane sums once there are enough of them to fill the device
     const uint64_t norm_lanes = (uint64_t)e->num_cus * pg::kThreads;

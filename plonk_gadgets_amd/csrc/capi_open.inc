@@ -50,9 +50,11 @@ pg_status pg_poly_open(pg_engine *e, const pg_scalar *const *d_cols, const pg_sc
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
-    PG_TRY(grow_units(e->d_open, e->open_units, 2 * A.tiles));
+    PG_TRY(e->d_open.carve(16, [&](Carve cv) {
+        A.tot = cv.take<uint4>(2 * A.tiles);
+        return cv.bytes();
+    }));
     A.f = reinterpret_cast<uint4 *>(d_witness);
-    A.tot = e->d_open;
     A.value = reinterpret_cast<uint4 *>(d_value);
     A.chunk = (A.tiles + pg::kThreads - 1) / pg::kThreads;
     A.xpow2[0] = to_fr(point);
@@ -60,9 +62,9 @@ pg_status pg_poly_open(pg_engine *e, const pg_scalar *const *d_cols, const pg_sc
     A.chunk_pow[0] = fr_pow_u64(A.xpow2[11], A.chunk);
     for (int k = 1; k < 8; k++) A.chunk_pow[k] = pg::fr_mul(A.chunk_pow[k - 1], A.chunk_pow[k - 1]);
     const uint64_t cap1 = (uint64_t)e->num_cus * 8, cap3 = (uint64_t)e->num_cus * 2;  // (pass 3: 68 KiB of LDS, two per CU)
-    hipLaunchKernelGGL(pg::open_combine_kernel<true>, dim3((uint32_t)(A.tiles < cap1 ? A.tiles : cap1)), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::open_combine_kernel<true>, dim3(grid_cap(A.tiles, cap1)), dim3(pg::kThreads), 0, st, A);
     hipLaunchKernelGGL(pg::open_carry_kernel, dim3(1), dim3(pg::kThreads), 0, st, A);
-    hipLaunchKernelGGL(pg::open_quotient_kernel, dim3((uint32_t)(A.tiles < cap3 ? A.tiles : cap3)), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::open_quotient_kernel, dim3(grid_cap(A.tiles, cap3)), dim3(pg::kThreads), 0, st, A);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }
@@ -76,7 +78,7 @@ pg_status pg_poly_combine(pg_engine *e, const pg_scalar *const *d_cols, const pg
     StreamScope scope{e, st};
     A.f = reinterpret_cast<uint4 *>(d_out);
     const uint64_t cap = (uint64_t)e->num_cus * 8;
-    hipLaunchKernelGGL(pg::open_combine_kernel<false>, dim3((uint32_t)(A.tiles < cap ? A.tiles : cap)), dim3(pg::kThreads), 0, st, A);
+    hipLaunchKernelGGL(pg::open_combine_kernel<false>, dim3(grid_cap(A.tiles, cap)), dim3(pg::kThreads), 0, st, A);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }

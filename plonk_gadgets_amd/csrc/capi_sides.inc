@@ -62,8 +62,11 @@ pg_status pg_plonk_sides(pg_engine *e, const uint8_t *d_proofs, uint64_t n, cons
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     // workspace: the decode status of every commitment
-    PG_TRY(grow_units(e->d_sides, e->sides_units, (n * pg::kSidesCommitments + 15) / 16));
-    uint8_t *cstat = reinterpret_cast<uint8_t *>(e->d_sides);
+    uint8_t *cstat;
+    PG_TRY(e->d_sides.carve(16, [&](Carve cv) {
+        cstat = cv.take<uint8_t>(n * pg::kSidesCommitments);
+        return cv.bytes();
+    }));
     pg::G1A *bases = reinterpret_cast<pg::G1A *>(d_bases);
     hipLaunchKernelGGL(pg::plonk_sides_decode_kernel, dim3(grid_of(e, n * pg::kSidesCommitments, 8)), dim3(pg::kThreads), 0, st, d_proofs, n,
                        bases, cstat);
