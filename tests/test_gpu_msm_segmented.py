@@ -1,8 +1,8 @@
 """GPU: pg_msm_segmented (csrc/msm_small.hpp) through Engine.msm_segmented against the G1 model (tests/g1_model.py), limb for
 limb.  Bases are known multiples k_i G, so a segment's sum is (sum_i s_i k_i mod r) G: one scalar multiplication in the model.
 Ragged segments with 1, 2 and 3 columns at a stride; every signed-digit boundary of any window width and the top carry; the
-degenerate additions (P + P, P - P, identity bases, zero scalars); agreement with Engine.msm; the launch shapes; the argument
-errors."""
+degenerate additions (P + P, P - P, identity bases, zero scalars); agreement with Engine.msm; the launch shapes; more sums than the
+normalisation has lanes (2 and 3 sums per inversion, empty segments among them); the argument errors."""
 import ctypes as C
 import os
 import random
@@ -189,6 +189,62 @@ def test_more_segments_than_resident_waves(engine, basis):
         for i in range(off[s], off[s + 1]):
             want = M.add(want, prods[i % 16])
         assert got[s][0] == M.point_limbs(want), s
+
+
+EMPTY_CYCLE = (0, 1, 2, 1, 0, 0, 3)
+
+
+def cycled_sums(pair_s, ks, n_segs):
+    """the model's sums for segments whose lengths cycle through EMPTY_CYCLE over points cycling through 16 (base, scalar)
+    pairs: uint64[n_segs, len(pair_s), 12].  Seven segments take seven points, so the sums repeat every 7 * 16 segments"""
+    period = 16 * len(EMPTY_CYCLE)
+    rows = np.zeros((period, len(pair_s), 12), dtype=np.uint64)
+    for j, col in enumerate(pair_s):
+        prods = [M.mul(col[i] * ks[i] % R, M.G) for i in range(16)]
+        at = 0
+        for s in range(period):
+            want = None
+            for _ in range(EMPTY_CYCLE[s % 7]):
+                want = M.add(want, prods[at % 16])
+                at += 1
+            rows[s, j] = M.point_limbs(want)
+        assert at == period  # (so segment s + period starts at the same place of the points' cycle)
+    return np.tile(rows, (n_segs // period + 1, 1, 1))[:n_segs]
+
+
+@pytest.mark.parametrize("extra,n_cols,per_lane", [(1, 1, 2), (5, 2, 3)])
+def test_more_sums_than_normalising_lanes(engine, basis, extra, n_cols, per_lane):
+    """num_cus * 256 + 1 sums and 2 (num_cus * 256 + 5): pg_msm_segmented then normalises 2 and 3 sums per inversion, the last
+    batch of the first call holding one.  Segment lengths cycle through 0, 1, 2, 1, 0, 0, 3, so empty segments (identities) fall
+    first, last and side by side inside the batches"""
+    ks, pts, dev = basis
+    T = torch.cuda.get_device_properties(0).multi_processor_count * 256
+    n_segs = T + extra
+    sums = n_segs * n_cols
+    assert -(-sums // T) == per_lane and per_lane <= 32, (T, sums)  # (what capi_msm_small.inc computes: not 1 on any device)
+    assert sums % per_lane == 1 or extra != 1
+    rng = random.Random(17 + extra)
+    pair_s = [[rng.randrange(R) for _ in range(16)] for _ in range(n_cols)]
+    want = cycled_sums(pair_s, ks, n_segs)
+    # the construction itself, against the naive sums of the first 7 * 16 segments
+    lengths = [EMPTY_CYCLE[s % 7] for s in range(n_segs)]
+    off = offsets_of(lengths)
+    n = off[-1]
+    for j in range(n_cols):
+        for s in range(112):
+            idx = [i % 16 for i in range(off[s], off[s + 1])]
+            assert want[s, j].tolist() == M.point_limbs(M.msm([pair_s[j][i] for i in idx], [pts[i] for i in idx])), (s, j)
+    idx = np.arange(n) % 16
+    sc = np.full((n_cols, n + 3, 4), np.uint64(2**64 - 1), dtype=np.uint64)
+    for j in range(n_cols):
+        sc[j, :n] = synth.scalars_from_ints(pair_s[j])[idx]
+    got = engine.msm_segmented(dev[torch.from_numpy(idx).to(DEV)], torch.from_numpy(sc.view(np.int64)).to(DEV)[:, :n], off)
+    assert got.shape == (n_segs, n_cols, 12)
+    got = got.cpu().numpy().view(np.uint64)
+    bad = np.nonzero((got != want).any(axis=2))
+    assert bad[0].size == 0, (bad[0][:8].tolist(), bad[1][:8].tolist())
+    empty = np.array(lengths) == 0
+    assert empty.sum() > n_segs // 3 and not got[empty].any()
 
 
 def test_one_long_segment_of_srs_powers(engine):
