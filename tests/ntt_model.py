@@ -102,19 +102,37 @@ def point_identity_holds(c, e, s: int, omega: int) -> bool:
     return lhs == (pow(s, n, Q) - 1) * rhs % Q
 
 
-def build_point_check(out_dir: str):
-    """tests/cpp/ntt_point_check.c with oracle/fr.c as a second source -> ctypes function ntt_point_check(c, e, n, s, omega,
-    threads): the identity above on Montgomery-limb arrays (uint64 [n, 4]); 1 holds, 0 fails, -1 s lies in the subgroup"""
+def _point_check_lib(out_dir: str):
+    """tests/cpp/ntt_point_check.c with oracle/fr.c as a second source, as a ctypes library"""
     import ctypes as C
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     so = os.path.join(out_dir, "libntt_point_check.so")
-    subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-shared", "-fPIC", "-pthread", "-I", os.path.join(root, "oracle"),
-                           os.path.join(root, "tests", "cpp", "ntt_point_check.c"), os.path.join(root, "oracle", "fr.c"), "-o", so])
-    fn = C.CDLL(so).ntt_point_check
+    if not os.path.exists(so):
+        subprocess.check_call(["gcc", "-std=c11", "-O2", "-Wall", "-shared", "-fPIC", "-pthread", "-I", os.path.join(root, "oracle"),
+                               os.path.join(root, "tests", "cpp", "ntt_point_check.c"), os.path.join(root, "oracle", "fr.c"), "-o", so])
+    return C.CDLL(so)
+
+
+def build_point_check(out_dir: str):
+    """ctypes function ntt_point_check(c, e, n, s, omega, threads): the identity above on Montgomery-limb arrays
+    (uint64 [n, 4]); 1 holds, 0 fails, -1 s lies in the subgroup"""
+    import ctypes as C
+    fn = _point_check_lib(out_dir).ntt_point_check
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_int]
+    return fn
+
+
+def build_point_check_scaled(out_dir: str):
+    """ctypes function ntt_point_check_scaled(c, e, n, s, omega, g, threads): the same identity with c_i g^i for c_i, that is
+    e = coset_fft(c, g).  One check for all four kinds: fft (c = in, e = out, g = 1), ifft (c = out, e = in, g = 1), coset_fft
+    (c = in, e = out, g), coset_ifft (c = out, e = in, g)"""
+    import ctypes as C
+    fn = _point_check_lib(out_dir).ntt_point_check_scaled
+    fn.restype = C.c_int
+    fn.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     return fn
 
 

@@ -1,7 +1,8 @@
 """GPU: pg_ntt (csrc/ntt.hpp) through Engine.fft / ifft / coset_fft / coset_ifft against the Python-int model of tests/ntt_model.py,
 limb for limb, at every size from 1 to 2^16 points (every number and split of passes); bit-exact round trips on the device up to
-2^24; the random-point identity at 2^18 and 2^20; the error cases; in place vs copying; the composer's wire, sigma and selector
-polynomials; and one 2^29 column, forward and inverse, its forward result checked on the host by tests/cpp/ntt_point_check.c."""
+2^24; the random-point identity at 2^18 and 2^20; every kind at 2^19, 2^21, 2^22, 2^23 (two strided passes, uneven and even splits)
+and fft and coset_ifft at 2^25 (three strided passes) through the random-point identity on the host (tests/cpp/ntt_point_check.c);
+the error cases; in place vs copying; the composer's wire, sigma and selector polynomials; and one 2^29 column, forward and inverse, its forward result checked on the host by tests/cpp/ntt_point_check.c."""
 import ctypes as C
 import os
 import sys
@@ -106,6 +107,90 @@ def test_random_point_identity(engine, m):
     g = [pow(7, i, M.Q) for i in range(1 << m)]
     ce = PM.ints_of(host(engine.coset_fft(x)))
     assert M.point_identity_holds([a * b % M.Q for a, b in zip(c, g)], ce, s, M.omega_of(m))
+
+
+def ntt_passes(m):
+    """the strided passes of ntt_enqueue (capi.hip) before its last pass of 2^10 points: the top m - 10 bits in passes of at
+    most 7 bits, as even as possible, the larger ones first"""
+    tile_bits, strided_bits = 10, 7  # kNttTileBits, kNttStridedBits
+    if m <= tile_bits:
+        return []
+    top = m - tile_bits
+    count = (top + strided_bits - 1) // strided_bits
+    return [top // count + (1 if p < top % count else 0) for p in range(count)]
+
+
+SPLITS = {19: [5, 4], 21: [6, 5], 22: [6, 6], 23: [7, 6], 25: [5, 5, 5]}
+
+
+def test_the_splits_the_sizes_below_reach():
+    assert {m: ntt_passes(m) for m in SPLITS} == SPLITS
+    # (what the other tests of this file reach: one pass up to 2^17, an even pair at 2^20 and 2^24, three passes from 2^25)
+    assert [len(ntt_passes(m)) for m in (10, 11, 17, 18, 24, 25, 29)] == [0, 1, 1, 2, 2, 3, 3]
+    assert ntt_passes(20) == [5, 5] and ntt_passes(24) == [7, 7]
+
+
+def device_random(shape, seed):
+    """random_limbs, drawn on the device"""
+    gen = torch.Generator(device=DEV).manual_seed(seed)
+    x = torch.randint(-(2**63), 2**63 - 1, tuple(shape) + (4,), dtype=torch.int64, device=DEV, generator=gen)
+    x[..., 3] = (x[..., 3] & (2**63 - 1)) % 0x73EDA753299D7D48
+    return x
+
+
+def need_hbm():
+    free, _ = torch.cuda.mem_get_info()
+    if free < (8 << 30):
+        pytest.skip("less than 8 GiB of HBM free")
+
+
+@pytest.fixture(scope="module")
+def scaled_check(tmp_path_factory):
+    return M.build_point_check_scaled(str(tmp_path_factory.mktemp("ntt_point_check")))
+
+
+# (2^25 is 1 GiB per column and its host check takes seconds: the plain forward and the coset inverse kind only)
+SPLIT_CASES = [(m, kind) for m in sorted(SPLITS) for kind in KINDS if m < 25 or kind in ("fft", "coset_ifft")]
+
+
+@pytest.mark.parametrize("m,kind", SPLIT_CASES, ids=["%d-%s" % c for c in SPLIT_CASES])
+def test_uneven_and_three_pass_splits(engine, scaled_check, m, kind):
+    """one random column of every kind at the sizes of SPLITS: out = kind(in) holds iff the forward side is the (coset) transform
+    of the coefficient side, checked at a random point s on the host; one flipped limb of the output breaks it.  At 2^19 also
+    three columns in place at a stride of n + 5 points, the points behind each column untouched."""
+    need_hbm()
+    assert ntt_passes(m) == SPLITS[m]
+    n = 1 << m
+    rng = np.random.default_rng(7000 + 4 * m + KINDS.index(kind))
+    mont = lambda v: np.array(PM.mont(v), dtype=np.uint64)
+    s = mont(int.from_bytes(rng.bytes(40), "little") % M.Q)
+    om, g = mont(M.omega_of(m)), mont(M.DEFAULT_G if kind.startswith("coset") else 1)
+    inverse = kind.endswith("ifft")
+
+    def holds(src, dst):
+        c, e = (dst, src) if inverse else (src, dst)
+        return scaled_check(c.ctypes.data, e.ctypes.data, n, s.ctypes.data, om.ctypes.data, g.ctypes.data, M.point_check_threads())
+
+    x = device_random((n,), seed=100 * m + KINDS.index(kind))
+    src = host(x)
+    dst = host(call(engine, kind, x))
+    del x
+    assert holds(src, dst) == 1
+    where = int(rng.integers(0, n))
+    dst[where, int(rng.integers(0, 3))] ^= np.uint64(1) << np.uint64(int(rng.integers(0, 64)))
+    assert holds(src, dst) == 0, where
+    if m != 19:
+        return
+    buf = torch.full((3, n + 5, 4), -1, dtype=torch.int64, device=DEV)
+    buf[:, :n] = device_random((3, n), seed=1900 + KINDS.index(kind))
+    before = [np.ascontiguousarray(host(buf[j, :n])) for j in range(3)]
+    assert call(engine, kind, buf[:, :n], inplace=True).data_ptr() == buf.data_ptr()
+    assert bool((buf[:, n:] == -1).all()), "a point beyond n of a column was written"
+    for j in range(3):
+        after = np.ascontiguousarray(host(buf[j, :n]))
+        assert holds(before[j], after) == 1, j
+        after[(where + j) % n, 0] ^= np.uint64(1)
+        assert holds(before[j], after) == 0, j
 
 
 def test_error_cases(engine):

@@ -1,7 +1,9 @@
 """GPU: pg_sigma_evaluations and pg_permutation_product (csrc/permutation_product.hpp) against the Python-int model of
 tests/perm_product_model.py, limb for limb, on small circuits of every append kind the f-row tests build; the copy constraints of
 those circuits hold (wrap == 1, StandardComposer.copy_constraints_hold), and stop holding when a wire value or sigma is corrupted;
-the error cases; and the 270 M-row composer of bench.py padded to 2^29, its z checked by the recurrence on the host."""
+the error cases; synthetic cycles over 2^24 rows (the first size at which launch 1 reuses its denominator slabs and a lane of
+launch 2 carries more than one tile), z checked by the recurrence on the host; and the 270 M-row composer of bench.py padded to
+2^29, checked the same way."""
 import os
 import sys
 
@@ -180,6 +182,136 @@ def test_error_cases(engine):
     # and the engine goes on
     assert engine.permutation_product(vals, sigma, S(BETA), S(GAMMA))[1].to_int() == 1
     comp.close()
+
+
+def synthetic_cycles(padded_n, n_values, seed, device):
+    """wire values and a sigma whose cycles pair DISTANT rows, built with torch: for r < padded_n / 2 and its mirror row
+    q = padded_n - 1 - r,
+      r % 3 == 0: (j, r) <-> (j, q) in every wire j, with equal values;
+      r % 3 == 1: (j, r) -> (j + 1 mod 4, q) and (j, q) -> (j + 1 mod 4, r): two cycles of four, the value a of (0, r) on the one
+                  through (0, r) and the value b of (0, q) on the other;
+      r % 3 == 2: fixed points with unrelated values.
+    The rows >= n_values read as zero, so their mirror rows are zero too.  -> (four int64[n_values, 4], sigma int64[4, padded_n])"""
+    N = padded_n
+    gen = torch.Generator(device=device).manual_seed(seed)
+    vals = torch.randint(-(2**63), 2**63 - 1, (4, N, 4), dtype=torch.int64, device=device, generator=gen)
+    vals[..., 3] = (vals[..., 3] & (2**63 - 1)) % synth.Q_TOP
+    sigma = torch.arange(4 * N, dtype=torch.int64, device=device).view(4, N).clone()
+    r = torch.arange(N // 2, dtype=torch.int64, device=device)
+    r0, r1 = r[r % 3 == 0], r[r % 3 == 1]
+    q0, q1 = N - 1 - r0, N - 1 - r1
+    a, b = vals[0, r1].clone(), vals[0, q1].clone()
+    for j in range(4):
+        sigma[j, r0], sigma[j, q0] = j * N + q0, j * N + r0
+        vals[j, q0] = vals[j, r0]
+        up = (j + 1) % 4 * N
+        sigma[j, r1], sigma[j, q1] = up + q1, up + r1
+        vals[j, r1], vals[j, q1] = (a, b) if j % 2 == 0 else (b, a)
+    vals[:, : N - n_values] = 0
+    return [vals[j, :n_values].contiguous() for j in range(4)], sigma
+
+
+def test_synthetic_cycles_equal_the_model_at_256_rows(engine):
+    """the construction of the 2^24-row test below, small enough for the model: its copy constraints hold, z moves, and a
+    bumped value breaks them -- in the model and on the device alike"""
+    N, n_values = 256, 256 - 4 * 3
+    wires, sigma = synthetic_cycles(N, n_values, seed=256, device=DEV)
+    hs, omega = host(sigma), M.omega_of(8)
+    ints = [M.ints_of(host(w)) for w in wires]
+    ez, ewrap = M.grand_product(ints, hs, N, BETA, GAMMA, omega)
+    assert ewrap == 1 and ez[0] == 1 and len(set(ez)) > N // 4
+    ratios_not_one = sum(ez[i + 1] != ez[i] for i in range(N - 1))
+    assert ratios_not_one >= N // 2
+    z, wrap = engine.permutation_product(wires, sigma, S(BETA), S(GAMMA))
+    assert wrap.to_int() == 1 and np.array_equal(host(z), M.limbs_of(ez))
+    ints[2][100] = (ints[2][100] + 1) % M.Q
+    bz, bwrap = M.grand_product(ints, hs, N, BETA, GAMMA, omega)
+    assert bwrap != 1
+    wires[2] = dev(M.limbs_of(ints[2]))
+    z, wrap = engine.permutation_product(wires, sigma, S(BETA), S(GAMMA))
+    assert wrap.to_int() == bwrap and np.array_equal(host(z), M.limbs_of(bz))
+
+
+def product_launches(padded_n, cus):
+    """pg_permutation_product's launch arithmetic (capi.hip, permutation_product.hpp): (tiles of 16384 rows, workgroups of
+    launch 1 -- two per CU, each reusing its slab of denominators for tiles grid apart --, tiles per lane of launch 2)"""
+    tile, threads = 16384, 256  # kPpTile, kThreads
+    tiles = (padded_n + tile - 1) // tile
+    return tiles, min(tiles, 2 * cus), (tiles + threads - 1) // threads
+
+
+def test_strided_tiles_and_many_tiles_per_carry_lane(engine):
+    """padded_n = the first power of two with more tiles than launch 1 has workgroups (2 per CU) and than launch 2 has lanes
+    (256): 2^24 on 256 CUs.  wrap == 1 and z[0] == 1; a bumped value in tile 0 and one in a tile past launch 1's grid each
+    make wrap != 1; z[i+1] den_i == z[i] num_i in Python integers at the last row of every tile, at every 64-row lane boundary of
+    the first and last tiles, the tiles on either side of launch 1's grid and two random ones, around n_values and at 1000
+    random rows; the sigma evaluations at the same rows."""
+    import gc
+    gc.collect()
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info()
+    if free < (8 << 30):
+        pytest.skip("less than 8 GiB of HBM free")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    m = next(m for m in range(14, 33) if product_launches(1 << m, cus)[0] > max(2 * cus, 256))
+    padded_n = 1 << m
+    tiles, grid, per = product_launches(padded_n, cus)
+    print("permutation product: %d CUs, padded_n = 2^%d, %d tiles, launch 1 grid %d, %d tiles per carry lane"
+          % (cus, m, tiles, grid, per))
+    assert tiles > 2 * cus and tiles > 256 and grid == 2 * cus < tiles and per > 1
+    assert product_launches(padded_n // 2, cus)[0] <= max(2 * cus, 256)
+    tile = 16384
+    n_values = padded_n - 4 * 3089  # (not tile-aligned)
+    wires, sigma = synthetic_cycles(padded_n, n_values, seed=m, device=DEV)
+    omega = M.omega_of(m)
+    z, wrap = engine.permutation_product(wires, sigma, S(BETA), S(GAMMA))
+    assert wrap.to_int() == 1
+    assert M.ints_of(host(z[:1])) == [1]
+    rng = np.random.default_rng(m)
+    special = [0, tiles - 1, 2 * cus - 1, 2 * cus] + [int(t) for t in rng.integers(1, tiles - 1, size=2)]
+    rows = [np.arange(1, tiles + 1) * tile - 1]                                       # the last row of every tile
+    rows += [t * tile + np.arange(1, 257) * 64 - 1 for t in special]                  # the last row of every lane's run
+    rows += [t * tile + np.arange(0, 256) * 64 for t in special]                      # ... and the first
+    rows.append(n_values + np.arange(-3, 3))
+    rows.append(rng.integers(0, padded_n, size=1000))
+    idx = np.unique(np.concatenate(rows))
+    idx = idx[idx < padded_n - 1]
+    ti = torch.from_numpy(idx.astype(np.int64)).to(DEV)
+    zi = M.ints_of(host(z.index_select(0, ti)))
+    zn = M.ints_of(host(z.index_select(0, ti + 1)))
+    si = host(sigma.index_select(1, ti))
+    live = torch.clamp(ti, max=n_values - 1)
+    wv = [M.ints_of(host(w.index_select(0, live))) for w in wires]
+    moved = 0
+    for r, i in enumerate(idx.tolist()):
+        w = [[wv[j][r] if i < n_values else 0] for j in range(4)]
+        sev = [M.K[int(x) // padded_n] * pow(omega, int(x) % padded_n, M.Q) % M.Q for x in si[:, r]]
+        num, den = M.factors(w, sev, 0, BETA, GAMMA, pow(omega, i, M.Q))
+        assert zn[r] * den % M.Q == zi[r] * num % M.Q, i
+        moved += num != den
+    assert moved >= len(idx) // 2  # (z actually moves: most sampled rows have a ratio other than 1)
+    del z
+    # one value bumped: in tile 0 (a zeroed mirror row on a swap), and in a tile launch 1 reaches on its second round
+    far = next(i for i in range((2 * cus + 1) * tile + 5, n_values) if (padded_n - 1 - i) % 3 == 0)
+    assert far // tile >= 2 * cus
+    for j, row in ((0, 3), (2, far)):
+        bad = list(wires)
+        bad[j] = wires[j].clone()
+        bad[j][row, 0] += 1
+        assert engine.permutation_product(bad, sigma, S(BETA), S(GAMMA))[1].to_int() != 1, (j, row)
+        del bad
+    del wires
+    gc.collect()
+    torch.cuda.empty_cache()
+    # the sigma evaluations at the same rows, every wire
+    ev = engine.sigma_evaluations(sigma)
+    for j in range(4):
+        got = host(ev[j].index_select(0, ti))
+        exp = [M.K[int(x) // padded_n] * pow(omega, int(x) % padded_n, M.Q) % M.Q for x in si[j]]
+        assert np.array_equal(got, M.limbs_of(exp)), j
+    del ev, sigma
+    gc.collect()
+    torch.cuda.empty_cache()
 
 
 def test_full_size_next_rows_composer(engine):

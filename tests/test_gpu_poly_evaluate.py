@@ -1,6 +1,7 @@
 """GPU: pg_poly_evaluate (csrc/quotient.hpp) through Engine.evaluate: Horner in Python integers at every size from 1 to 2^14 that
 matters (powers of two, their neighbours, the segment boundaries), several columns at a stride; x = 0 gives c_0; at x = omega^j the
-result is fft(c)[j] at 2^20; the error cases; and one 2^28 column checked by tests/cpp/poly_eval_check.c on the host."""
+result is fft(c)[j] at 2^20; the error cases; several columns of 259 segments (more partial sums than reduce lanes, more work items
+than workgroups) and one 2^28 column, checked by tests/cpp/poly_eval_check.c on the host."""
 import ctypes as C
 import gc
 import os
@@ -100,6 +101,52 @@ def build_check(out_dir):
     fn.restype = C.c_int
     fn.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_int, C.c_void_p]
     return fn
+
+
+def eval_launches(n, n_cols, cus):
+    """pg_poly_evaluate's launch arithmetic (capi.hip, quotient.hpp): (segments of 16384 points per column, work items
+    it = col * segs + seg, workgroups of poly_eval_kernel -- eight per CU, each striding over the items)"""
+    seg = 16384  # kEvalSeg
+    segs = (n + seg - 1) // seg
+    return segs, n_cols * segs, min(n_cols * segs, 8 * cus)
+
+
+def test_many_segments_in_several_columns(engine, tmp_path):
+    """columns of 259 segments: a lane of poly_eval_reduce_kernel sums more than one partial, and x^(16384 seg) comes from a
+    table of more than 256 entries; enough columns that poly_eval_kernel's workgroups stride over the items (8 on 256 CUs).
+    Every column against Horner on the host, at a random x and at x = 1."""
+    gc.collect()
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info()
+    if free < (8 << 30):
+        pytest.skip("less than 8 GiB of HBM free")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 16384 * 258 + 77
+    cols = max(3, 8 * cus // 259 + 1)
+    segs, items, grid = eval_launches(n, cols, cus)
+    print("poly_evaluate: %d CUs, %d columns of %d points, %d segments each, %d items on %d workgroups"
+          % (cus, cols, n, segs, items, grid))
+    assert segs == 259 > 256 and items == cols * segs > 8 * cus == grid
+    assert eval_launches(n, cols - 1, cus)[1] <= 8 * cus or cols == 3
+    check = build_check(str(tmp_path))
+    gen = torch.Generator(device=DEV).manual_seed(259)
+    buf = torch.randint(-(2**63), 2**63 - 1, (cols, n + 3, 4), dtype=torch.int64, device=DEV, generator=gen)
+    buf[..., 3] = (buf[..., 3] & (2**63 - 1)) % 0x73EDA753299D7D48
+    buf[:, n:] = -1
+    c_h = buf.cpu().numpy().view(np.uint64)
+    rng = np.random.default_rng(259)
+    out = np.zeros(4, dtype=np.uint64)
+    for x in (int.from_bytes(rng.bytes(40), "little") % PM.Q, 1):
+        got = engine.evaluate(buf[:, :n], x)
+        pt = np.array(PM.mont(x), dtype=np.uint64)
+        for j in range(cols):
+            assert check(c_h[j].ctypes.data, n, pt.ctypes.data, M.point_check_threads(), out.ctypes.data) == 0
+            assert got[j].limbs() == [int(v) for v in out], (x == 1, j)
+    assert bool((buf[:, n:] == -1).all())
+    assert len({tuple(v.limbs()) for v in got}) == cols  # (the columns differ: a column read for another would show)
+    del buf, c_h
+    gc.collect()
+    torch.cuda.empty_cache()
 
 
 def test_full_size_column(engine, tmp_path):

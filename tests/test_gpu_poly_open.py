@@ -1,8 +1,9 @@
 """GPU: pg_poly_open and pg_poly_combine (csrc/opening.hpp) through Engine.open / Engine.combine / CommitKey.aggregate_witness.
 Limb for limb against tests/opening_model.py at sizes that cross the 2048-point tiles, the lane runs and the carry scan's
 levels, with 1 to 32 columns (a column repeated), weights 0, 1 and r - 1, and points 0, 1, r - 1, roots of unity and random
-ones; the remainder against Engine.evaluate; the error cases; and 20 columns at n = 2^28 through the division identity at
-random points and the recurrence at the first, last and tile-edge coefficients.
+ones; the remainder against Engine.evaluate; the error cases; three columns at the first size whose pass 1 strides over its tiles
+(2^22 + 4097 points on 256 CUs), through the division identity at a random point on the host; and 20 columns at n = 2^28
+through the division identity at random points and the recurrence at the first, last and tile-edge coefficients.
 
 The model runs on the Montgomery residues themselves: f, q and the remainder are linear in the columns, so with canonical
 weights and point the residues obey the same recurrence, and no conversion is needed."""
@@ -164,6 +165,59 @@ def test_error_cases(engine):
     with pytest.raises(ValueError):
         engine.open([x[0]], [1, 2], 3)
     torch.cuda.synchronize()
+
+
+def open_launches(n, cus):
+    """pg_poly_open's launch arithmetic (capi_open.inc, opening.hpp): (tiles of 2048 points, workgroups of pass 1 -- eight per
+    CU, each striding over the tiles --, workgroups of pass 3, tiles per lane of pass 2)"""
+    tile = 2048  # kOpenTile
+    tiles = (n + tile - 1) // tile
+    return tiles, min(tiles, 8 * cus), min(tiles, 2 * cus), (tiles + 255) // 256
+
+
+def test_pass_one_strides_over_its_tiles(engine, tmp_path):
+    """n = 2048 (8 CUs + 2) + 1: three tiles more than pass 1 has workgroups, the last of one point.  With W and val from the
+    device and every evaluation by Horner on the host (tests/cpp/poly_eval_check.c): val = sum mu_j p_j(x),
+    sum mu_j p_j(r) - val = W(r) (r - x) at a random r, and W[n - 1] = 0 -- W has degree < n - 1, so the random r pins it."""
+    from test_gpu_poly_evaluate import build_check
+    import ntt_model
+    gc.collect()
+    torch.cuda.empty_cache()
+    free, _ = torch.cuda.mem_get_info()
+    if free < (8 << 30):
+        pytest.skip("less than 8 GiB of HBM free")
+    cus = torch.cuda.get_device_properties(0).multi_processor_count
+    n = 2048 * (8 * cus + 2) + 1
+    tiles, grid1, grid3, chunk = open_launches(n, cus)
+    print("poly_open: %d CUs, n = %d, %d tiles, pass 1 on %d workgroups, pass 3 on %d, %d tiles per carry lane"
+          % (cus, n, tiles, grid1, grid3, chunk))
+    assert tiles == 8 * cus + 3 > grid1 == 8 * cus and open_launches(n - 4097, cus)[0] <= 8 * cus
+    check = build_check(str(tmp_path))
+    threads = ntt_model.point_check_threads()
+    rng = random.Random(n)
+    mu = [1, rng.randrange(2, R - 1), R - 1]
+    x, r = rng.randrange(R), rng.randrange(R)
+    polys = random_poly((3, n), seed=cus)
+    w, val = engine.open([polys[j] for j in range(3)], mu, x)
+    p_h = polys.cpu().numpy().view(np.uint64)
+    w_h = w.cpu().numpy().view(np.uint64)
+    del polys, w
+
+    def horner(c, at):
+        pt, out = np.array(PM.mont(at), dtype=np.uint64), np.zeros(4, dtype=np.uint64)
+        assert check(c.ctypes.data, n, pt.ctypes.data, threads, out.ctypes.data) == 0
+        return PM.from_mont(out)
+
+    f_x = sum(m * horner(p_h[j], x) for j, m in enumerate(mu)) % R
+    f_r = sum(m * horner(p_h[j], r) for j, m in enumerate(mu)) % R
+    assert val.to_int() == f_x
+    assert not w_h[n - 1].any()
+    assert (f_r - f_x) % R == horner(w_h, r) * (r - x) % R
+    # one coefficient of W spoiled, in a tile of pass 1's second round: the identity fails
+    w_h[2048 * (8 * cus + 1) + 5, 1] ^= np.uint64(1 << 20)
+    assert (f_r - f_x) % R != horner(w_h, r) * (r - x) % R
+    gc.collect()
+    torch.cuda.empty_cache()
 
 
 def test_full_size_twenty_columns(engine):

@@ -95,3 +95,35 @@ def test_host_point_check_helper(tmp_path):
     assert call(ca, bad, M.point_check_threads()) == 0
     one = np.array(PM.mont(1), dtype=np.uint64)  # s = 1 lies in the subgroup
     assert fn(ca.ctypes.data, ea.ctypes.data, 1 << m, one.ctypes.data, oa.ctypes.data, 4) == -1
+
+
+@pytest.mark.parametrize("g", [1, 7])
+def test_host_point_check_scaled_helper(tmp_path, g):
+    """ntt_point_check_scaled against point_identity_holds on c_i g^i, at n = 2^10: a true pair and a spoiled one"""
+    fn = M.build_point_check_scaled(str(tmp_path))
+    m = 10
+    c = rand(1 << m, 500 + g)
+    e = M.coset_fft(c, g)
+    s, om = 0x5EED_0007 ** 5 % M.Q, M.omega_of(m)
+    scaled = [ci * pow(g, i, M.Q) % M.Q for i, ci in enumerate(c)]
+    assert M.point_identity_holds(scaled, e, s, om)
+    ca, ea = PM.limbs_of(c), PM.limbs_of(e)
+    sa, oa, ga = (np.array(PM.mont(v), dtype=np.uint64) for v in (s, om, g))
+    call = lambda x, y, th: fn(x.ctypes.data, y.ctypes.data, 1 << m, sa.ctypes.data, oa.ctypes.data, ga.ctypes.data, th)
+    for threads in (1, 3, 16):
+        assert call(ca, ea, threads) == 1
+    for where in (0, 77, (1 << m) - 1):  # one limb of one element, of either array
+        bad = ea.copy()
+        bad[where, 1] ^= 1 << 17
+        spoiled = PM.ints_of(bad)
+        assert not M.point_identity_holds(scaled, spoiled, s, om)
+        assert call(ca, bad, M.point_check_threads()) == 0
+        bad = ca.copy()
+        bad[where, 0] ^= 1
+        assert call(bad, ea, 5) == 0
+    if g != 1:  # the scaling matters: the plain identity does not hold for the coset transform
+        one = np.array(PM.mont(1), dtype=np.uint64)
+        assert fn(ca.ctypes.data, ea.ctypes.data, 1 << m, sa.ctypes.data, oa.ctypes.data, one.ctypes.data, 4) == 0
+        assert M.build_point_check(str(tmp_path))(ca.ctypes.data, ea.ctypes.data, 1 << m, sa.ctypes.data, oa.ctypes.data, 4) == 0
+    else:
+        assert M.build_point_check(str(tmp_path))(ca.ctypes.data, ea.ctypes.data, 1 << m, sa.ctypes.data, oa.ctypes.data, 4) == 1
