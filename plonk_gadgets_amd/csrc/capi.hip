@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cassert>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -100,6 +101,8 @@ struct pg_engine {
     Scratch d_open;
     // scratch of pg_plonk_sides: the decode status of every commitment, 11 bytes a proof
     Scratch d_sides;
+    // pg_composer_permutation: its kernels' dynamic LDS limits have been raised on this device (capi_composer.inc, perm_kernel_attributes)
+    bool perm_attributes_set = false;
 };
 
 namespace {
@@ -621,8 +624,8 @@ pg_status pg_range_check_layout(const pg_scalar *min_range, const pg_scalar *max
     // range.rs:87-90
     uint64_t n = pg::num_bits_closest_power_of_two(pg::fr_sub(mx, pg::fr_one()));
     out->num_bits = n;
-    out->gates_per_item = 4 * n + 11;
-    out->vars_per_item = 2 * n + 524;  // 2n+523 of range_check + 1 of allocate
+    out->gates_per_item = pg::kind_rows(pg::WIRES_RANGE_CHECK, n);
+    out->vars_per_item = pg::kind_vars(pg::WIRES_RANGE_CHECK, n);  // those of range_check and the one of allocate
     out->n_gates = out->gates_per_item * batch;
     out->n_vars = out->vars_per_item * batch;
     return PG_OK;
@@ -711,8 +714,8 @@ pg_status pg_scalar_decomposition_layout(uint64_t num_bits, uint64_t batch, pg_l
     if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (num_bits > 256) return fail(PG_ERR_INVALID_ARGUMENT, "num_bits > 256 (the reference panics: src/range.rs:134)");
     out->num_bits = num_bits;
-    out->gates_per_item = 2 * num_bits + 4;
-    out->vars_per_item = num_bits + 260;
+    out->gates_per_item = pg::kind_rows(pg::WIRES_DECOMPOSITION, num_bits);
+    out->vars_per_item = pg::kind_vars(pg::WIRES_DECOMPOSITION, num_bits);
     out->n_gates = out->gates_per_item * batch;
     out->n_vars = out->vars_per_item * batch;
     return PG_OK;
@@ -751,8 +754,8 @@ pg_status pg_max_bound_layout(const pg_scalar *max_range, uint64_t batch, pg_lay
     if (!is_reduced(mx)) return fail(PG_ERR_INVALID_ARGUMENT, "bound is not a reduced BlsScalar");
     uint64_t n = pg::num_bits_closest_power_of_two(pg::fr_sub(mx, pg::fr_one()));
     out->num_bits = n;
-    out->gates_per_item = 2 * n + 5;
-    out->vars_per_item = n + 262;  // n+261 of max_bound + 1 of allocate
+    out->gates_per_item = pg::kind_rows(pg::WIRES_MAX_BOUND, n);
+    out->vars_per_item = pg::kind_vars(pg::WIRES_MAX_BOUND, n);  // those of max_bound and the one of allocate
     out->n_gates = out->gates_per_item * batch;
     out->n_vars = out->vars_per_item * batch;
     return PG_OK;

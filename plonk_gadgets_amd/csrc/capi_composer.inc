@@ -418,25 +418,36 @@ pg_status flush_gates(pg_composer *c, size_t i, size_t j) {
     return flush_gate_list(c, at);
 }
 
-// The footprint of a run of queued single calls that went out as one batched launch: the same rows as the batched append of that
-// gadget, so the f-rows (pg_composer_materialize, pg_composer_permutation) may treat them alike -- closed forms instead of the gather and
-// the sparse list (a circuit built the reference's way, one allocate + range_check at a time: sigma of 17 M rows 3.5 -> 0.3 ms).  Short
-// runs stay what they were (rows of single calls): a footprint per run of two calls would be a launch per run in sigma.
-void add_run_segment(pg_composer *c, uint64_t gate0, uint64_t var0, uint64_t count, uint32_t L, uint32_t V, uint64_t foreign_per_item,
-                     uint32_t wire_kind, uint32_t wire_n, uint32_t tail = 0) {
-    if (!c->segs.empty() && !c->segs.back().row_off && c->segs.back().gate_end == gate0 && c->segs.back().var_end == var0 &&
-        c->segs.back().L == L && c->segs.back().V == V && c->segs.back().wire_kind == wire_kind && c->segs.back().wire_n == wire_n &&
-        c->segs.back().tail == tail) {
-        c->segs.back().gate_end += count * L;
-        c->segs.back().var_end += count * V;
-        c->segs.back().items += count;
+// The footprint joins the last one where it continues it in every respect (calls of one kind one after the other; a loop of single
+// calls, flushed run by run), else it is one of its own.  only_if_long -- a run of queued single calls that went out as one batched
+// launch: the same rows as the batched append of that gadget (a circuit built the reference's way, one allocate + range_check at a
+// time: sigma of 17 M rows 3.5 -> 0.3 ms), but short runs stay what they were (rows of single calls): a footprint per run of two
+// calls would be a launch per run in sigma.
+void add_footprint(pg_composer *c, const pg::PermSeg &f, bool only_if_long = false) {
+    if (!f.items) return;
+    // what lets perm_route's questions be asked in any order (footprint.hpp)
+    assert(!pg::is_template_kind(f.wire_kind) || f.wire_n == 0);
+    assert(!f.row_off || f.wire_kind == pg::WIRES_UNKNOWN || pg::is_template_kind(f.wire_kind) || (f.wire_kind == pg::WIRES_MAX_BOUND && f.tail == 0));
+    pg::PermSeg *last = c->segs.empty() ? nullptr : &c->segs.back();
+    if (last && !last->row_off && !f.row_off && last->gate_end == f.gate_base && last->var_end == f.var_base && last->L == f.L && last->V == f.V &&
+        last->wire_kind == f.wire_kind && last->wire_n == f.wire_n && last->tail == f.tail) {
+        last->gate_end = f.gate_end;
+        last->var_end = f.var_end;
+        last->items += f.items;
     } else {
-        if (count * L < 4096) return;
-        if (!c->segs.empty() && c->segs.back().gate_end > gate0) return;  // (footprints stay in row order; cannot happen: flushes go in call order)
-        c->segs.push_back(pg::PermSeg{gate0, gate0 + count * L, var0, var0 + count * V, L, V, count, nullptr, nullptr, 1, wire_kind, wire_n, 0, tail});
+        if (only_if_long && f.gate_end - f.gate_base < pg::kFootprintMinRows) return;
+        if (only_if_long && last && last->gate_end > f.gate_base) return;  // (footprints stay in row order; cannot happen: flushes go in call order)
+        c->segs.push_back(f);
     }
-    c->sparse_hint += count * foreign_per_item;
+    c->sparse_hint += f.items * pg::kind_sparse_hint(f.wire_kind);  // references to Variables created before the call
 }
+
+// a queued gadget call (Queued::kind 1: range_check, 2: max_bound) as a kind of footprint, and what it weighs (footprint.hpp); a fused
+// pair's first Variable is its witness
+static_assert(pg::WIRES_RANGE_CHECK == 1 && pg::WIRES_MAX_BOUND == 2, "Queued::kind is the wire kind of the fused call");
+uint32_t gadget_kind(const pg_composer::Queued &q, bool fused) { return pg::ladder_kind(q.kind, fused); }
+uint32_t gadget_rows(const pg_composer::Queued &q) { return pg::kind_rows(q.kind, q.num_bits); }
+uint32_t gadget_vars(const pg_composer::Queued &q, bool fused) { return pg::kind_vars(gadget_kind(q, fused), q.num_bits); }
 
 // a run of `count` queued gadget calls of one kind and one set of public bounds starting at queue[i]; fused = each is
 // preceded by the add_input that allocated its witness (the reference's loop: allocate, then range_check -- stride 2)
@@ -465,24 +476,14 @@ pg_status flush_gadgets(pg_composer *c, size_t i, size_t count, bool fused, size
     from_fr(q0.b1, &mx);
     pg_status st;
     const bool values_only = q0.in_place;  // (a run is of one kind in this too: same_gadget)
-    const uint32_t rows_per_call = q0.kind == 1 ? 4 * q0.num_bits + 11 : 2 * q0.num_bits + 5;
-    const uint32_t stride_rows = gates_between ? rows_per_call + (uint32_t)gates_between : 0u;
+    const uint32_t stride_rows = gates_between ? gadget_rows(q0) + (uint32_t)gates_between : 0u;
     if (q0.kind == 1)
         st = range_check_common(c->e, &mn, &mx, fused ? nullptr : d_var, d_wit, count, gate0, var0, &out, nullptr, c->stream, values_only,
                                 stride_rows);
     else
         st = max_bound_common(c->e, &mx, fused ? nullptr : d_var, d_wit, count, gate0, var0, &out, nullptr, c->stream, values_only, stride_rows);
     c->flush_launches++;
-    if (st == PG_OK && !gates_between) {
-        // rows / Variables per call: pg_range_check_layout / pg_max_bound_layout; a fused pair's first Variable is its witness
-        const uint32_t n = q0.num_bits, own = fused ? 1u : 0u;
-        if (q0.kind == 1)
-            add_run_segment(c, gate0, var0, count, 4 * n + 11, 2 * n + 523 + own, fused ? 0 : 4,
-                            fused ? pg::WIRES_RANGE_CHECK : pg::WIRES_RANGE_CHECK_ALLOCATED, n);
-        else
-            add_run_segment(c, gate0, var0, count, 2 * n + 5, n + 261 + own, fused ? 0 : 2,
-                            fused ? pg::WIRES_MAX_BOUND : pg::WIRES_MAX_BOUND_ALLOCATED, n);
-    }
+    if (st == PG_OK && !gates_between) add_footprint(c, pg::footprint(gate0, var0, count, gadget_kind(q0, fused), q0.num_bits), true);
     return st;
 }
 
@@ -509,8 +510,6 @@ size_t loop_gates(const pg_composer *c, size_t i, bool fused) {
 bool body_at(const pg_composer *c, size_t i, bool fused) {
     return fused ? fused_pair(c, i) : (i < c->queue.size() && c->queue[i].kind != 0);
 }
-uint32_t gadget_rows(const pg_composer::Queued &q) { return q.kind == 1 ? 4 * q.num_bits + 11 : 2 * q.num_bits + 5; }
-uint32_t gadget_vars(const pg_composer::Queued &q, bool fused) { return (q.kind == 1 ? 2 * q.num_bits + 523 : q.num_bits + 261) + (fused ? 1u : 0u); }
 // body number `k` of a loop that starts at queue[i] lies where the stride says: rows L + g apart, Variables as many as a body creates
 bool same_stride(const pg_composer *c, size_t i, size_t body, size_t k, bool fused) {
     const size_t go = fused ? 1 : 0;
@@ -553,12 +552,8 @@ size_t flush_loop(pg_composer *c, size_t i, bool fused, pg_status *st) {
                 own_result = own_result && gc.a == res && gc.b == res && gc.c == res;
             }
         }
-        if (own_result) {
-            const uint32_t kind = q0.kind == 1 ? (fused ? pg::WIRES_RANGE_CHECK : pg::WIRES_RANGE_CHECK_ALLOCATED)
-                                               : (fused ? pg::WIRES_MAX_BOUND : pg::WIRES_MAX_BOUND_ALLOCATED);
-            add_run_segment(c, q0.gate, fused ? c->queue[i].g.var : q0.var, count, gadget_rows(q0) + (uint32_t)g, vars,
-                            fused ? 0 : (q0.kind == 1 ? 4 : 2), kind, q0.num_bits, (uint32_t)g);
-        }
+        if (own_result)
+            add_footprint(c, pg::footprint(q0.gate, fused ? c->queue[i].g.var : q0.var, count, gadget_kind(q0, fused), q0.num_bits, (uint32_t)g), true);
     }
     return body * count;
 }
@@ -935,7 +930,7 @@ pg_status pg_range_check(pg_composer *c, const pg_scalar *min_range, const pg_sc
         c->last_kind = 1;
     }
     const pg_layout lay = c->last_lay;
-    const uint64_t rows = lay.gates_per_item, vars = lay.vars_per_item - 1;  // the witness is already allocated
+    const uint64_t rows = lay.gates_per_item, vars = pg::kind_vars(pg::WIRES_RANGE_CHECK_ALLOCATED, lay.num_bits);  // the witness is already allocated
     PG_TRY(need(c, rows, vars));
     PG_TRY(check_var(c, witness->var));
     if (!is_reduced(to_fr(&witness->scalar))) return fail(PG_ERR_INVALID_ARGUMENT, "witness is not a reduced BlsScalar");
@@ -988,7 +983,7 @@ pg_status pg_max_bound(pg_composer *c, const pg_scalar *max_range, const pg_allo
         c->last_kind = 2;
     }
     const pg_layout lay = c->last_lay;
-    const uint64_t rows = lay.gates_per_item, vars = lay.vars_per_item - 1;
+    const uint64_t rows = lay.gates_per_item, vars = pg::kind_vars(pg::WIRES_MAX_BOUND_ALLOCATED, lay.num_bits);
     PG_TRY(need(c, rows, vars));
     PG_TRY(check_var(c, witness->var));
     if (!is_reduced(to_fr(&witness->scalar))) return fail(PG_ERR_INVALID_ARGUMENT, "witness is not a reduced BlsScalar");
@@ -1126,131 +1121,85 @@ pg_status pg_is_non_zero(pg_composer *c, pg_variable var, const pg_scalar *value
 
 static pg_status perm_reserve(pg_composer *c, Scratch &buf, size_t bytes);
 
-// every item of a batched call creates all of its V Variables itself on its own L rows: a segment for the permutation
-static void add_segment(pg_composer *c, uint64_t batch, uint64_t n_gates, uint64_t n_vars, uint64_t foreign_per_item = 0,
-                        uint32_t wire_kind = pg::WIRES_UNKNOWN, uint32_t wire_n = 0) {
-    if (!batch) return;
-    c->sparse_hint += batch * foreign_per_item;  // references to Variables created before the call
-    const uint32_t L = (uint32_t)(n_gates / batch), V = (uint32_t)(n_vars / batch);
-    if (!c->segs.empty() && !c->segs.back().row_off && c->segs.back().gate_end == c->n && c->segs.back().var_end == c->nvars &&
-        c->segs.back().L == L && c->segs.back().V == V && c->segs.back().wire_kind == wire_kind && c->segs.back().wire_n == wire_n &&
-        c->segs.back().tail == 0) {
-        c->segs.back().gate_end += n_gates;
-        c->segs.back().var_end += n_vars;
-        c->segs.back().items += batch;
-    } else {
-        c->segs.push_back(pg::PermSeg{c->n, c->n + n_gates, c->nvars, c->nvars + n_vars, L, V, batch, nullptr, nullptr, 1, wire_kind, wire_n, 0, 0});
+}  // extern "C"
+
+namespace {
+// The uniform ladder batches: `batch` items of `wire_kind` at the composer's end.  layout: the call's pg_*_layout (ladder length, rows);
+// emit: its *_common call; sig_kind, b0, b1: what its signature hashes beside the batch and the place.  A kind whose witnesses are
+// Variables from elsewhere (the `_allocated` calls, decomposition) has their array checked and digested first.
+template <class Layout, class Emit>
+pg_status ladder_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg::Fr &b0, const pg::Fr &b1, const pg_variable *d_witness_var,
+                       uint64_t batch, uint64_t *num_bits, Layout layout, Emit emit) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(flush(c));
+    pg_layout lay;
+    PG_TRY(layout(&lay));
+    const uint64_t n_vars = pg::kind_vars(wire_kind, lay.num_bits) * batch;  // (an `_allocated` call: without the allocate's)
+    pg_composer::Sig dg{0, 0};
+    if (pg::ladder_foreign_per_item(wire_kind)) {
+        if (batch) PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+        PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
     }
+    PG_TRY(need(c, lay.n_gates, n_vars));
+    const pg_columns at = cols_at(c, c->n, c->nvars);
+    // (a witness refresh: the same call at the same place has left these rows here, pg_composer_clear_witness)
+    SignedAppend sa(c, gadget_sig(c, sig_kind, b0, b1, batch, 0, dg), lay.n_gates, batch != 0);
+    PG_TRY(emit(&at, sa.in_place));
+    sa.commit();
+    add_footprint(c, pg::footprint(c->n, c->nvars, batch, wire_kind, (uint32_t)lay.num_bits));
+    c->n += lay.n_gates;
+    c->nvars += n_vars;
+    if (num_bits) *num_bits = lay.num_bits;
+    return PG_OK;
 }
-// ragged call: the composer keeps the call's prefix sums (device, items + 1 entries each) for the permutation
-static void add_ragged_segment(pg_composer *c, uint64_t batch, uint64_t n_gates, uint64_t n_vars, uint32_t max_rows, uint32_t max_vars,
-                               const uint64_t *d_row_off, const uint64_t *d_var_off, uint64_t foreign_per_item,
-                               uint32_t wire_kind = pg::WIRES_UNKNOWN) {
-    if (!batch) return;
-    c->sparse_hint += batch * foreign_per_item;
-    c->segs.push_back(pg::PermSeg{c->n, c->n + n_gates, c->nvars, c->nvars + n_vars, max_rows, max_vars, batch, d_row_off, d_var_off, 1, wire_kind, 0, 0, 0});
+pg_status range_check_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg_scalar *min_range, const pg_scalar *max_range,
+                            const pg_variable *d_witness_var, const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
+    return ladder_batch(
+        c, wire_kind, sig_kind, opt_fr(min_range), opt_fr(max_range), d_witness_var, batch, nullptr,
+        [&](pg_layout *lay) { return pg_range_check_layout(min_range, max_range, batch, lay); },
+        [&](const pg_columns *at, bool in_place) {
+            return range_check_common(c->e, min_range, max_range, d_witness_var, d_witness, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
+        });
 }
+pg_status max_bound_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg_scalar *max_range, const pg_variable *d_witness_var,
+                          const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars, uint64_t *num_bits) {
+    return ladder_batch(
+        c, wire_kind, sig_kind, pg::fr_zero(), opt_fr(max_range), d_witness_var, batch, num_bits,
+        [&](pg_layout *lay) { return pg_max_bound_layout(max_range, batch, lay); },
+        [&](const pg_columns *at, bool in_place) {
+            return max_bound_common(c->e, max_range, d_witness_var, d_witness, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
+        });
+}
+}  // namespace
+
+extern "C" {
 
 pg_status pg_composer_range_check_batch(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
                                         const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    pg_layout lay;
-    PG_TRY(pg_range_check_layout(min_range, max_range, batch, &lay));
-    PG_TRY(need(c, lay.n_gates, lay.n_vars));
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    // (a witness refresh: the same call at the same place has left these rows here, pg_composer_clear_witness)
-    SignedAppend sa(c, gadget_sig(c, 11, to_fr(min_range), to_fr(max_range), batch, 0), lay.n_gates, batch != 0);
-    PG_TRY(range_check_common(c->e, min_range, max_range, nullptr, d_witness, batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
-    sa.commit();
-    add_segment(c, batch, lay.n_gates, lay.n_vars, 0, pg::WIRES_RANGE_CHECK, (uint32_t)lay.num_bits);
-    c->n += lay.n_gates;
-    c->nvars += lay.n_vars;
-    return PG_OK;
+    return range_check_batch(c, pg::WIRES_RANGE_CHECK, 11, min_range, max_range, nullptr, d_witness, batch, d_result_vars);
 }
-
 pg_status pg_composer_range_check_allocated_batch(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
                                                   const pg_variable *d_witness_var, const pg_scalar *d_witness,
                                                   uint64_t batch, pg_variable *d_result_vars) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    pg_layout lay;
-    PG_TRY(pg_range_check_layout(min_range, max_range, batch, &lay));
-    const uint64_t n_vars = lay.n_vars - batch;  // no allocate
-    if (batch) PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
-    pg_composer::Sig dg;
-    PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
-    PG_TRY(need(c, lay.n_gates, n_vars));
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    SignedAppend sa(c, gadget_sig(c, 21, to_fr(min_range), to_fr(max_range), batch, 0, dg), lay.n_gates, batch != 0);
-    PG_TRY(range_check_common(c->e, min_range, max_range, d_witness_var, d_witness, batch, c->n, c->nvars, &at, d_result_vars, c->stream,
-                              sa.in_place));
-    sa.commit();
-    add_segment(c, batch, lay.n_gates, n_vars, 4, pg::WIRES_RANGE_CHECK_ALLOCATED, (uint32_t)lay.num_bits);
-    c->n += lay.n_gates;
-    c->nvars += n_vars;
-    return PG_OK;
+    return range_check_batch(c, pg::WIRES_RANGE_CHECK_ALLOCATED, 21, min_range, max_range, d_witness_var, d_witness, batch, d_result_vars);
 }
-
 pg_status pg_composer_max_bound_batch(pg_composer *c, const pg_scalar *max_range, const pg_scalar *d_witness, uint64_t batch,
                                       pg_variable *d_result_vars, uint64_t *num_bits) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    pg_layout lay;
-    PG_TRY(pg_max_bound_layout(max_range, batch, &lay));
-    PG_TRY(need(c, lay.n_gates, lay.n_vars));
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    SignedAppend sa(c, gadget_sig(c, 12, pg::fr_zero(), to_fr(max_range), batch, 0), lay.n_gates, batch != 0);
-    PG_TRY(max_bound_common(c->e, max_range, nullptr, d_witness, batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
-    sa.commit();
-    add_segment(c, batch, lay.n_gates, lay.n_vars, 0, pg::WIRES_MAX_BOUND, (uint32_t)lay.num_bits);
-    c->n += lay.n_gates;
-    c->nvars += lay.n_vars;
-    if (num_bits) *num_bits = lay.num_bits;
-    return PG_OK;
+    return max_bound_batch(c, pg::WIRES_MAX_BOUND, 12, max_range, nullptr, d_witness, batch, d_result_vars, num_bits);
 }
-
 pg_status pg_composer_max_bound_allocated_batch(pg_composer *c, const pg_scalar *max_range, const pg_variable *d_witness_var,
                                                 const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars,
                                                 uint64_t *num_bits) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    pg_layout lay;
-    PG_TRY(pg_max_bound_layout(max_range, batch, &lay));
-    const uint64_t n_vars = lay.n_vars - batch;  // no allocate
-    if (batch) PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
-    pg_composer::Sig dg;
-    PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
-    PG_TRY(need(c, lay.n_gates, n_vars));
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    SignedAppend sa(c, gadget_sig(c, 22, pg::fr_zero(), to_fr(max_range), batch, 0, dg), lay.n_gates, batch != 0);
-    PG_TRY(max_bound_common(c->e, max_range, d_witness_var, d_witness, batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
-    sa.commit();
-    add_segment(c, batch, lay.n_gates, n_vars, 2, pg::WIRES_MAX_BOUND_ALLOCATED, (uint32_t)lay.num_bits);
-    c->n += lay.n_gates;
-    c->nvars += n_vars;
-    if (num_bits) *num_bits = lay.num_bits;
-    return PG_OK;
+    return max_bound_batch(c, pg::WIRES_MAX_BOUND_ALLOCATED, 22, max_range, d_witness_var, d_witness, batch, d_result_vars, num_bits);
 }
-
 pg_status pg_composer_scalar_decomposition_batch(pg_composer *c, uint64_t num_bits, const pg_variable *d_witness_var,
                                                  const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    pg_layout lay;
-    PG_TRY(pg_scalar_decomposition_layout(num_bits, batch, &lay));
-    if (batch) PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
-    pg_composer::Sig dg;
-    PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
-    PG_TRY(need(c, lay.n_gates, lay.n_vars));
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    SignedAppend sa(c, gadget_sig(c, 23, pg::fr_from_u64(num_bits), pg::fr_zero(), batch, 0, dg), lay.n_gates, batch != 0);
-    PG_TRY(decomposition_common(c->e, num_bits, d_witness_var, d_witness, batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
-    sa.commit();
-    add_segment(c, batch, lay.n_gates, lay.n_vars, 2, pg::WIRES_DECOMPOSITION, (uint32_t)num_bits);
-    c->n += lay.n_gates;
-    c->nvars += lay.n_vars;
-    return PG_OK;
+    return ladder_batch(
+        c, pg::WIRES_DECOMPOSITION, 23, pg::fr_from_u64(num_bits), pg::fr_zero(), d_witness_var, batch, nullptr,
+        [&](pg_layout *lay) { return pg_scalar_decomposition_layout(num_bits, batch, lay); },
+        [&](const pg_columns *at, bool in_place) {
+            return decomposition_common(c->e, num_bits, d_witness_var, d_witness, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
+        });
 }
 
 }  // extern "C"
@@ -1258,9 +1207,10 @@ pg_status pg_composer_scalar_decomposition_batch(pg_composer *c, uint64_t num_bi
 // the two-input scalar gadgets: assignments gathered from the composer's own table into its scratch, then the engine call
 namespace {
 template <class GD>
-pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, uint64_t rows, uint64_t vars, const pg_variable *d_a_var,
-                          const pg_variable *d_b_var, uint64_t batch, pg_variable *d_result_vars) {
+pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
+                          pg_variable *d_result_vars) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    const uint64_t rows = pg::kind_rows(wire_kind), vars = pg::kind_vars(wire_kind);
     PG_TRY(flush(c));
     if (batch == 0) return PG_OK;
     PG_TRY(check_u64s(d_a_var, "first Variable array"));
@@ -1282,7 +1232,7 @@ pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, uin
     PG_TRY(two_input_common<GD>(c->e, d_a_var, reinterpret_cast<const pg_scalar *>(va), d_b_var, reinterpret_cast<const pg_scalar *>(vb),
                                 batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
     sa.commit();
-    add_segment(c, batch, rows * batch, vars * batch, pg::template_foreign_per_item(wire_kind), wire_kind);
+    add_footprint(c, pg::footprint(c->n, c->nvars, batch, wire_kind));
     c->n += rows * batch;
     c->nvars += vars * batch;
     return PG_OK;
@@ -1293,15 +1243,15 @@ extern "C" {
 
 pg_status pg_composer_conditionally_select_zero_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_select_var,
                                                       uint64_t batch, pg_variable *d_result_vars) {
-    return two_input_batch<pg::SelectZeroGD>(c, 24, pg::WIRES_SELECT_ZERO, 1, 1, d_x_var, d_select_var, batch, d_result_vars);
+    return two_input_batch<pg::SelectZeroGD>(c, 24, pg::WIRES_SELECT_ZERO, d_x_var, d_select_var, batch, d_result_vars);
 }
 pg_status pg_composer_conditionally_select_one_batch(pg_composer *c, const pg_variable *d_y_var, const pg_variable *d_selector_var,
                                                      uint64_t batch, pg_variable *d_result_vars) {
-    return two_input_batch<pg::SelectOneGD>(c, 25, pg::WIRES_SELECT_ONE, 4, 4, d_y_var, d_selector_var, batch, d_result_vars);
+    return two_input_batch<pg::SelectOneGD>(c, 25, pg::WIRES_SELECT_ONE, d_y_var, d_selector_var, batch, d_result_vars);
 }
 pg_status pg_composer_maybe_equal_batch(pg_composer *c, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
                                         pg_variable *d_result_vars) {
-    return two_input_batch<pg::MaybeEqualGD>(c, 26, pg::WIRES_MAYBE_EQUAL, 3, 3, d_a_var, d_b_var, batch, d_result_vars);
+    return two_input_batch<pg::MaybeEqualGD>(c, 26, pg::WIRES_MAYBE_EQUAL, d_a_var, d_b_var, batch, d_result_vars);
 }
 
 namespace {
@@ -1328,28 +1278,32 @@ pg_status ragged_alloc(uint64_t batch, bool with_bits, RaggedBuffers *b) {
     return PG_OK;
 }
 }  // namespace
+}  // extern "C"
 
-pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_max_range, const pg_scalar *d_witness,
-                                             uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    if (batch == 0) return PG_OK;
-    PG_HIP_TRY(hipSetDevice(c->e->device));
+namespace {
+// The batches whose items differ in shape (per-item public bounds; items that stop at is_non_zero's error, scalar.rs:73-80): the call's
+// prefix sums are planned on the device, the rows emitted by them, and the composer keeps them for the f-rows.
+//   plan(b, &lay, &errs)  the call's pg_*_plan: row_off / var_off (and the ladder lengths), the totals, the items that fail
+//   sign(errs, &sig)      the call's signature
+//   emit(b, &at, in_place) its *_common call
+// A batch without failing items of a kind whose full items are all alike leaves a uniform footprint.
+template <class Plan, class Sign, class Emit>
+pg_status ragged_batch(pg_composer *c, uint32_t wire_kind, uint64_t batch, uint64_t *err_count, Plan plan, Sign sign, Emit emit) {
+    const bool per_item_bounds = wire_kind == pg::WIRES_MAX_BOUND;
     RaggedBuffers b;
-    PG_TRY(ragged_alloc(batch, true, &b));
+    PG_TRY(ragged_alloc(batch, per_item_bounds, &b));
     pg_layout lay;
-    pg_status st = pg_max_bound_ragged_plan(c->e, d_max_range, batch, b.num_bits, b.row_off, b.var_off, &lay, c->stream);
+    uint64_t errs = 0;
+    pg_status st = plan(b, &lay, &errs);
+    const bool failed_items = st == PG_ERR_NON_EXISTING_INVERSE;
+    if (failed_items) st = PG_OK;
     if (st == PG_OK) st = need(c, lay.n_gates, lay.n_vars);
-    pg_composer::Sig dg;
-    if (st == PG_OK) st = digest_scalars(c, d_max_range, batch, &dg);  // the rows: the per-item public bounds and where the call lands
+    pg_composer::Sig sig;
+    if (st == PG_OK) st = sign(errs, &sig);
     if (st == PG_OK) {
         const pg_columns at = cols_at(c, c->n, c->nvars);
-        SignedAppend sa(c, gadget_sig(c, 27, pg::fr_zero(), pg::fr_zero(), batch, 0, dg), lay.n_gates);
-        st = max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.num_bits, b.row_off, b.var_off, c->n, c->nvars, &at,
-                                     d_result_vars, c->stream, sa.in_place);
-        if (st == PG_OK && d_num_bits_out &&
-            hipMemcpyAsync(d_num_bits_out, b.num_bits, batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-            st = fail(PG_ERR_HIP, "copy of the ladder lengths failed");
+        SignedAppend sa(c, sig, lay.n_gates);
+        st = emit(b, &at, sa.in_place);
         if (st == PG_OK) sa.commit();
     }
     if (st != PG_OK) {
@@ -1358,10 +1312,52 @@ pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_
         return st;
     }
     b.keep(c);
-    add_ragged_segment(c, batch, lay.n_gates, lay.n_vars, 2 * 255 + 5, 255 + 262, b.row_off, b.var_off, 0, pg::WIRES_MAX_BOUND);
+    // (per-item bounds: the largest item is the longest ladder there is)
+    pg::PermSeg f = pg::footprint(c->n, c->nvars, batch, wire_kind, per_item_bounds ? 255u : 0u);
+    if (per_item_bounds || errs) {
+        f.gate_end = f.gate_base + lay.n_gates;
+        f.var_end = f.var_base + lay.n_vars;
+        f.row_off = b.row_off;
+        f.var_off = b.var_off;
+        f.wire_n = 0;
+    }
+    add_footprint(c, f);
     c->n += lay.n_gates;
     c->nvars += lay.n_vars;
-    return PG_OK;
+    if (err_count) *err_count = errs;
+    return failed_items ? fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(errs) + " item(s) without an inverse") : PG_OK;
+}
+// an item's shape depends on its witness: only a batch WITHOUT failing items has rows that are a function of public things alone -- a
+// batch with one never matches (nor is matched)
+uint64_t unmatched_if(pg_composer *c, uint64_t errs) { return errs ? 0x8000000000000000ull | ++c->unmatched : 0; }
+}  // namespace
+
+extern "C" {
+
+pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_max_range, const pg_scalar *d_witness,
+                                             uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(flush(c));
+    if (batch == 0) return PG_OK;
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    return ragged_batch(
+        c, pg::WIRES_MAX_BOUND, batch, nullptr,
+        [&](RaggedBuffers &b, pg_layout *lay, uint64_t *) {
+            return pg_max_bound_ragged_plan(c->e, d_max_range, batch, b.num_bits, b.row_off, b.var_off, lay, c->stream);
+        },
+        [&](uint64_t, pg_composer::Sig *sig) {  // the rows: the per-item public bounds and where the call lands
+            pg_composer::Sig dg;
+            PG_TRY(digest_scalars(c, d_max_range, batch, &dg));
+            *sig = gadget_sig(c, 27, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
+            return PG_OK;
+        },
+        [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
+            PG_TRY(max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.num_bits, b.row_off, b.var_off, c->n, c->nvars, at, d_result_vars,
+                                           c->stream, in_place));
+            if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits, batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
+            return PG_OK;
+        });
 }
 
 pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask,
@@ -1380,38 +1376,19 @@ pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
     hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_var, c->cols.vars, batch, vals);
     PG_HIP_TRY(hipGetLastError());
-    RaggedBuffers b;
-    PG_TRY(ragged_alloc(batch, false, &b));
-    pg_layout lay;
-    uint64_t errs = 0;
-    pg_status st = pg_is_non_zero_plan(c->e, reinterpret_cast<const pg_scalar *>(vals), batch, b.row_off, b.var_off, d_err_mask, &lay,
-                                       &errs, c->stream);
-    const bool failed_items = st == PG_ERR_NON_EXISTING_INVERSE;
-    if (failed_items) st = PG_OK;
-    if (st == PG_OK) st = need(c, lay.n_gates, lay.n_vars);
-    if (st == PG_OK) {
-        const pg_columns at = cols_at(c, c->n, c->nvars);
-        // (an item's shape depends on its value, scalar.rs:73-80: only a batch without failing items has public rows)
-        SignedAppend sa(c, gadget_sig(c, 28, pg::fr_zero(), pg::fr_zero(), batch, errs ? 0x8000000000000000ull | ++c->unmatched : 0, dg),
-                        lay.n_gates);
-        st = is_non_zero_common(c->e, d_var, reinterpret_cast<const pg_scalar *>(vals), batch, b.row_off, b.var_off, c->n, c->nvars,
-                                c->zero_var, &at, c->stream, sa.in_place);
-        if (st == PG_OK) sa.commit();
-    }
-    if (st != PG_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        b.release();
-        return st;
-    }
-    b.keep(c);
-    if (errs == 0)  // every item complete: three rows and three Variables each
-        add_segment(c, batch, lay.n_gates, lay.n_vars, 2, pg::WIRES_IS_NON_ZERO);
-    else
-        add_ragged_segment(c, batch, lay.n_gates, lay.n_vars, 3, 3, b.row_off, b.var_off, 2, pg::WIRES_IS_NON_ZERO);
-    c->n += lay.n_gates;
-    c->nvars += lay.n_vars;
-    if (err_count) *err_count = errs;
-    return failed_items ? fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(errs) + " item(s) without an inverse") : PG_OK;
+    const pg_scalar *d_vals = reinterpret_cast<const pg_scalar *>(vals);
+    return ragged_batch(
+        c, pg::WIRES_IS_NON_ZERO, batch, err_count,
+        [&](RaggedBuffers &b, pg_layout *lay, uint64_t *errs) {
+            return pg_is_non_zero_plan(c->e, d_vals, batch, b.row_off, b.var_off, d_err_mask, lay, errs, c->stream);
+        },
+        [&](uint64_t errs, pg_composer::Sig *sig) {
+            *sig = gadget_sig(c, 28, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs), dg);
+            return PG_OK;
+        },
+        [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
+            return is_non_zero_common(c->e, d_var, d_vals, batch, b.row_off, b.var_off, c->n, c->nvars, c->zero_var, at, c->stream, in_place);
+        });
 }
 
 pg_status pg_composer_scalar_mix_batch(pg_composer *c, const pg_scalar *d_v, const pg_scalar *d_y, const pg_scalar *d_s,
@@ -1422,37 +1399,19 @@ pg_status pg_composer_scalar_mix_batch(pg_composer *c, const pg_scalar *d_v, con
     if (err_count) *err_count = 0;
     if (batch == 0) return PG_OK;
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    RaggedBuffers b;
-    PG_TRY(ragged_alloc(batch, false, &b));
-    pg_layout lay;
-    uint64_t errs = 0;
-    pg_status st = pg_scalar_mix_plan(c->e, d_v, batch, b.row_off, b.var_off, d_err_mask, &lay, &errs, c->stream);
-    const bool failed_items = st == PG_ERR_NON_EXISTING_INVERSE;
-    if (failed_items) st = PG_OK;
-    if (st == PG_OK) st = need(c, lay.n_gates, lay.n_vars);
-    if (st == PG_OK) {
-        const pg_columns at = cols_at(c, c->n, c->nvars);
-        // an item's shape depends on its witness (is_non_zero stops at v = 0, scalar.rs:79): only a batch WITHOUT failing items
-        // has rows that are a function of public things alone -- a batch with one never matches (nor is matched)
-        SignedAppend sa(c, gadget_sig(c, 13, pg::fr_zero(), pg::fr_zero(), batch, errs ? 0x8000000000000000ull | ++c->unmatched : 0), lay.n_gates);
-        st = scalar_mix_common(c->e, d_v, d_y, d_s, d_a, d_b, batch, b.row_off, b.var_off, c->n, c->nvars, c->zero_var, &at, d_result_vars,
-                               c->stream, sa.in_place);
-        if (st == PG_OK) sa.commit();
-    }
-    if (st != PG_OK) {
-        (void)hipStreamSynchronize(c->stream);
-        b.release();
-        return st;
-    }
-    b.keep(c);
-    if (errs == 0)  // every item complete: ten rows and fifteen Variables each, the wires a function of the row (the f-rows' closed forms)
-        add_segment(c, batch, lay.n_gates, lay.n_vars, 0, pg::WIRES_MIX, 0);
-    else
-        add_ragged_segment(c, batch, lay.n_gates, lay.n_vars, 10, 15, b.row_off, b.var_off, 0, pg::WIRES_MIX);
-    c->n += lay.n_gates;
-    c->nvars += lay.n_vars;
-    if (err_count) *err_count = errs;
-    return failed_items ? fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(errs) + " item(s) without an inverse") : PG_OK;
+    return ragged_batch(
+        c, pg::WIRES_MIX, batch, err_count,
+        [&](RaggedBuffers &b, pg_layout *lay, uint64_t *errs) {
+            return pg_scalar_mix_plan(c->e, d_v, batch, b.row_off, b.var_off, d_err_mask, lay, errs, c->stream);
+        },
+        [&](uint64_t errs, pg_composer::Sig *sig) {
+            *sig = gadget_sig(c, 13, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs));
+            return PG_OK;
+        },
+        [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
+            return scalar_mix_common(c->e, d_v, d_y, d_s, d_a, d_b, batch, b.row_off, b.var_off, c->n, c->nvars, c->zero_var, at, d_result_vars,
+                                     c->stream, in_place);
+        });
 }
 
 namespace {
@@ -1489,7 +1448,7 @@ pg_status gate_batch(pg_composer *c, uint32_t op, const pg_variable *d_a, const 
     sa.commit();
     // one row per item; add / mul: one Variable, a and b come from outside; the others: three Variables from outside, none created --
     // a footprint for the f-rows only where it pays for the launch it costs there (short runs of rows stay rows of single calls)
-    if (creates || batch >= 4096) add_segment(c, batch, batch, creates ? batch : 0, creates ? 2 : 3, creates ? pg::WIRES_GATE_OUT : pg::WIRES_GATE_ROWS);
+    if (creates || batch >= pg::kFootprintMinRows) add_footprint(c, pg::footprint(c->n, c->nvars, batch, creates ? pg::WIRES_GATE_OUT : pg::WIRES_GATE_ROWS));
     c->n += batch;
     if (creates) c->nvars += batch;
     return PG_OK;
@@ -1661,36 +1620,32 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
                            lo, hi, c->zero_var);
     };
     uint64_t at = 0;
-    for (const pg::PermSeg &s : c->segs) {
-        if (s.V > pg::kMatWindowVars || s.V == 0 || s.gate_end - s.gate_base < 4096) continue;  // (left to the generic launch of the gap it widens)
-        generic(at, s.gate_base);
-        uint64_t group = pg::kMatWindowVars / (s.V ? s.V : 1);
-        group = group < 1 ? 1 : (group > s.items ? s.items : group);
 #ifndef PG_MAT_GRID_PER_CU
 #define PG_MAT_GRID_PER_CU 64
 #endif
+    // materialize_items_kernel's instantiations: MAT_SELF's two ragged forms, MAT_READ_WIRES for any footprint, MAT_SELF by uniform kind
+    using MatKernel = void (*)(const pg::ComposerCols, const pg::MaterializeOut, const pg::PermSeg, uint32_t, uint64_t);
+    static const MatKernel self_ragged[2] = {pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MAX_BOUND, true>,
+                                             pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MIX, true>};
+    static const MatKernel read_wires = pg::materialize_items_kernel<pg::MAT_READ_WIRES, pg::WIRES_UNKNOWN>;
+    static const MatKernel self[pg::WIRES_MIX + 1] = {
+        nullptr,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_RANGE_CHECK>,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MAX_BOUND>,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_RANGE_CHECK_ALLOCATED>,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MAX_BOUND_ALLOCATED>,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_DECOMPOSITION>,
+        pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MIX>,
+    };
+    for (const pg::PermSeg &s : c->segs) {
+        const uint64_t group = pg::mat_group(s);
+        const pg::MatRoute r = pg::mat_route(s, group);
+        if (!r.windowed) continue;  // (left to the generic launch of the gap it widens)
+        generic(at, s.gate_base);
         const uint64_t n_groups = (s.items + group - 1) / group, most = (uint64_t)c->e->num_cus * PG_MAT_GRID_PER_CU;
-        const dim3 mgrid((uint32_t)(n_groups < most ? n_groups : most));
-        // the wires in closed form (not even the indices are read), at most one Variable per item from elsewhere: one instantiation per kind
-        const bool closed = s.wire_kind != pg::WIRES_UNKNOWN && !s.row_off && (pg::ladder_foreign_per_item(s.wire_kind) == 0 || group <= pg::kMatWitItems);
-#define PG_MAT_LAUNCH(MODE, KIND)                                                                                                          \
-    hipLaunchKernelGGL((pg::materialize_items_kernel<MODE, KIND>), mgrid, dim3(pg::kMatThreads), 0, c->stream, c->cols, M, s, (uint32_t)group, \
-                       c->zero_var)
-        if (s.row_off && s.wire_kind == pg::WIRES_MAX_BOUND && group <= pg::kMatWitItems)  // per-item bounds: closed form from the prefix sums
-            hipLaunchKernelGGL((pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MAX_BOUND, true>), mgrid, dim3(pg::kMatThreads), 0, c->stream,
-                               c->cols, M, s, (uint32_t)group, c->zero_var);
-        else if (s.row_off && s.wire_kind == pg::WIRES_MIX && group < 127)  // the fused mix with items that stopped at their error: two shapes
-            hipLaunchKernelGGL((pg::materialize_items_kernel<pg::MAT_SELF, pg::WIRES_MIX, true>), mgrid, dim3(pg::kMatThreads), 0, c->stream,
-                               c->cols, M, s, (uint32_t)group, c->zero_var);
-        else if (!closed) PG_MAT_LAUNCH(pg::MAT_READ_WIRES, pg::WIRES_UNKNOWN);
-        else if (s.wire_kind == pg::WIRES_RANGE_CHECK) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_RANGE_CHECK);
-        else if (s.wire_kind == pg::WIRES_MAX_BOUND) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_MAX_BOUND);
-        else if (s.wire_kind == pg::WIRES_RANGE_CHECK_ALLOCATED) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_RANGE_CHECK_ALLOCATED);
-        else if (s.wire_kind == pg::WIRES_MAX_BOUND_ALLOCATED) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_MAX_BOUND_ALLOCATED);
-        else if (s.wire_kind == pg::WIRES_DECOMPOSITION) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_DECOMPOSITION);
-        else if (s.wire_kind == pg::WIRES_MIX) PG_MAT_LAUNCH(pg::MAT_SELF, pg::WIRES_MIX);
-        else PG_MAT_LAUNCH(pg::MAT_READ_WIRES, pg::WIRES_UNKNOWN);
-#undef PG_MAT_LAUNCH
+        const MatKernel kernel = r.mode != pg::MAT_SELF ? read_wires : r.ragged ? self_ragged[r.kind == pg::WIRES_MIX] : self[r.kind];
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)(n_groups < most ? n_groups : most)), dim3(pg::kMatThreads), 0, c->stream, c->cols, M, s,
+                           (uint32_t)group, c->zero_var);
         at = s.gate_end;
     }
     generic(at, c->n);
@@ -1705,9 +1660,6 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
     return PG_OK;
 }
 
-#ifndef PG_PERM_LDS_PAD
-#define PG_PERM_LDS_PAD 0
-#endif
 // grows one of the composer's buffers once the stream has drained: work in flight may still read what is there
 static pg_status perm_reserve(pg_composer *c, Scratch &buf, size_t bytes) {
     if (bytes <= buf.size()) return PG_OK;
@@ -1722,42 +1674,45 @@ pg_status pg_composer_permutation_reserve(pg_composer *c, uint64_t sparse_positi
     return PG_OK;
 }
 
+// the sigma kernels that ask for more dynamic LDS than the default limit: said once per engine (its device is current)
+static pg_status perm_kernel_attributes(pg_engine *e) {
+    if (e->perm_attributes_set) return PG_OK;
+    const void *const ladder_lds[4] = {
+        reinterpret_cast<const void *>(pg::perm_ladder_kernel<false>), reinterpret_cast<const void *>(pg::perm_template_kernel<true>),
+        reinterpret_cast<const void *>(pg::perm_template_kernel<false>), reinterpret_cast<const void *>(pg::perm_ladder_kernel<true>)};
+    if (pg::kPermLadderLds)
+        for (const void *k : ladder_lds) PG_HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg::kPermLadderLds));
+    PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_identity_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                                   (int)pg::kPermIdentityLds));
+    e->perm_attributes_set = true;
+    return PG_OK;
+}
+
 pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d_sigma) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     PG_TRY(flush(c));
     PG_TRY(check_u64s(d_sigma, "d_sigma"));
     if (padded_n < c->n) return fail(PG_ERR_INVALID_ARGUMENT, "padded_n is smaller than the circuit");
     PG_HIP_TRY(hipSetDevice(c->e->device));
+    PG_TRY(perm_kernel_attributes(c->e));
     const uint32_t grid = (uint32_t)c->e->num_cus * 32;
     if (!c->h_total) PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_total), 32, hipHostMallocDefault));
     uint32_t pos_bits = 2, var_bits = 1;
     while ((1ull << pos_bits) < 4 * c->n) pos_bits++;
     while ((1ull << var_bits) < c->nvars + 1) var_bits++;  // (one number more than there are Variables: the holes' key)
     if (pos_bits + var_bits > 64) return fail(PG_ERR_INVALID_ARGUMENT, "circuit too large for 64-bit (Variable, position) keys");
-    // segments one workgroup can link in LDS; the rows of any other batched call count as rows of single calls
+    // every footprint is classified ONCE (footprint.hpp, perm_route) and each loop below switches on that; a footprint of which not even
+    // one item fits a workgroup's LDS is dropped: its rows count as rows of single calls
     std::vector<pg::PermSeg> segs;
+    std::vector<pg::PermRoute> routes;
     std::vector<std::pair<uint64_t, uint64_t>> gaps;
     uint64_t at = 0, gap_rows = 0;
     for (pg::PermSeg s : c->segs) {
-        // small items are linked several at a time: `group` consecutive items count as one item (about 1024 rows per
-        // workgroup); a call whose items do not fit a workgroup's LDS is treated like rows of single calls
-        const auto fits = [&](uint64_t k) {
-            return 4 * k * s.L < pg::kPermDone && k * s.V < pg::kPermNone &&
-                   pg::perm_local_lds_bytes((uint32_t)(k * s.L), (uint32_t)(k * s.V)) <= pg::kPermLocalLdsLimit;
-        };
-        if (!fits(1)) continue;
-        uint64_t k = 1024 / s.L;
-        k = k < 1 ? 1 : (k > s.items ? s.items : k);
-        while (k > 1 && !fits(k)) k--;
-        // segments whose rows are linked in closed form (perm_ladder_kernel, perm_template_kernel) put EVERY position that holds a
-        // Variable from elsewhere on the sparse list -- also one that holds a Variable of an earlier item of the same segment (calls
-        // of one kind merge into one segment: the second call's inputs may be the first one's results).  perm_splice_kernel must
-        // then take an item's local positions from the item's OWN rows, not from a group's
-        const bool closed_ladder = s.wire_kind != pg::WIRES_UNKNOWN && s.wire_kind < pg::WIRES_MIX && (s.row_off ? s.wire_kind == pg::WIRES_MAX_BOUND && s.tail == 0 : s.wire_n >= 2);
-        if (closed_ladder || (pg::is_template_kind(s.wire_kind) && s.tail == 0)) k = 1;
-        s.group = (uint32_t)k;
+        const pg::PermRoute route = pg::perm_route(s);
+        if (!(s.group = pg::perm_group(s, route))) continue;
         if (s.gate_base > at) gaps.emplace_back(at, s.gate_base);
         segs.push_back(s);
+        routes.push_back(route);
         at = s.gate_end;
     }
     if (c->n > at) gaps.emplace_back(at, c->n);
@@ -1777,40 +1732,29 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
         for (const pg::FourthWire &f : c->fourth) { lo = f.gate < lo ? f.gate : lo; hi = f.gate > hi ? f.gate : hi; }
         X.fw_lo = lo; X.fw_span = hi - lo;
     }
-    // the ladder segments' slots on the sparse list: ladder_foreign_per_item per item, ahead of what the other kernels reserve by counter
-    uint64_t reserved = 0;
-    for (pg::PermSeg &s : segs)
-        if (s.wire_kind != pg::WIRES_UNKNOWN && !s.row_off && s.wire_n >= 2) {
-            s.sparse_base = reserved;
-            reserved += s.items * pg::ladder_foreign_per_item(s.wire_kind);
-        } else if (pg::is_template_kind(s.wire_kind) && s.tail == 0) {  // the small gadgets and gate batches (perm_template_kernel)
-            s.sparse_base = reserved;
-            reserved += s.items * pg::template_foreign_per_item(s.wire_kind);
+    // the closed-form routes' slots on the sparse list, ahead of what the other kernels reserve by counter; for the ragged ones the
+    // first item of every piece of rows, looked up once per call (perm_piece_items_kernel)
+    uint64_t reserved = 0, total_pieces = 0;
+    for (size_t i = 0; i < segs.size(); i++) {
+        if (pg::perm_reserves_slots(routes[i])) {
+            segs[i].sparse_base = reserved;
+            reserved += segs[i].items * pg::perm_slots_per_item(segs[i], routes[i]);
         }
-    // per-item bounds (max_bound_ragged_batch): sigma in closed form as well, an item's ladder length from the call's prefix sums -- the
-    // first item of every piece of rows is looked up once per call (perm_piece_items_kernel); likewise the small gadgets' segments
-    // with items that stopped at is_non_zero's error (perm_template_kernel<true>)
-    const auto ragged_ladder = [](const pg::PermSeg &s) { return s.row_off && s.wire_kind == pg::WIRES_MAX_BOUND && s.tail == 0; };
-    const auto template_seg = [](const pg::PermSeg &s) { return pg::is_template_kind(s.wire_kind) && s.tail == 0; };
-    const auto needs_pieces = [&](const pg::PermSeg &s) { return ragged_ladder(s) || (template_seg(s) && s.row_off); };
-    const auto pieces_of = [](const pg::PermSeg &s) { return (s.gate_end - (s.gate_base & ~1ull) + pg::kPermLadderRows - 1) / pg::kPermLadderRows; };
-    {
-        uint64_t total_pieces = 0;
-        for (const pg::PermSeg &s : segs)
-            if (needs_pieces(s)) total_pieces += pieces_of(s);
-        if (total_pieces) {
-            PG_TRY(perm_reserve(c, c->perm_pieces, total_pieces * sizeof(uint32_t)));
-            uint32_t *at_piece = c->perm_pieces.as<uint32_t>();
-            for (pg::PermSeg &s : segs)
-                if (needs_pieces(s)) {
-                    s.piece_item = at_piece;
-                    at_piece += pieces_of(s);
-                    const uint64_t want = (s.items + pg::kThreads - 1) / pg::kThreads;
-                    hipLaunchKernelGGL(pg::perm_piece_items_kernel, dim3((uint32_t)(want < grid ? want : grid)), dim3(pg::kThreads), 0, c->stream, s,
-                                       pg::kPermLadderRows, at_piece - pieces_of(s));
-                }
-            PG_HIP_TRY(hipGetLastError());
+        if (pg::perm_needs_piece_items(routes[i])) total_pieces += pg::perm_pieces(segs[i]);
+    }
+    if (total_pieces) {
+        PG_TRY(perm_reserve(c, c->perm_pieces, total_pieces * sizeof(uint32_t)));
+        uint32_t *at_piece = c->perm_pieces.as<uint32_t>();
+        for (size_t i = 0; i < segs.size(); i++) {
+            if (!pg::perm_needs_piece_items(routes[i])) continue;
+            pg::PermSeg &s = segs[i];
+            s.piece_item = at_piece;
+            at_piece += pg::perm_pieces(s);
+            const uint64_t want = (s.items + pg::kThreads - 1) / pg::kThreads;
+            hipLaunchKernelGGL(pg::perm_piece_items_kernel, dim3((uint32_t)(want < grid ? want : grid)), dim3(pg::kThreads), 0, c->stream, s,
+                               pg::kPermLadderRows, at_piece - pg::perm_pieces(s));
         }
+        PG_HIP_TRY(hipGetLastError());
     }
     unsigned long long *d_count = reinterpret_cast<unsigned long long *>(small + seg_bytes + fw_bytes);
     // the uploads read host vectors that must outlive them: the synchronisation below covers both
@@ -1835,52 +1779,38 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
         k1 = reinterpret_cast<uint64_t *>(c->perm_big.as<char>() + kb);
         const pg::PermSparse Q{k0, d_count, cap};
         hipLaunchKernelGGL(pg::perm_count_init_kernel, dim3(1), dim3(1), 0, c->stream, d_count, reserved);
-        for (const pg::PermSeg &s : segs) {
-            const uint64_t groups = (s.items + s.group - 1) / s.group, most = (uint64_t)c->e->num_cus * 64;
-            if (s.wire_kind != pg::WIRES_UNKNOWN && !s.row_off && s.wire_n >= 2) {  // a ladder gadget's rows: sigma in closed form
-                // (pieces are counted from the even gate at or before the segment's first; short pieces: one per workgroup, in dispatch order)
-                const uint64_t pieces = (s.gate_end - (s.gate_base & ~1ull) + pg::kPermLadderRows - 1) / pg::kPermLadderRows;
+        for (size_t i = 0; i < segs.size(); i++) {
+            const pg::PermSeg &s = segs[i];
+            const uint64_t most = (uint64_t)c->e->num_cus * 64, pieces = pg::perm_pieces(s);
+            const uint32_t lds = pg::perm_lds_bytes(s, routes[i]);
+            // (the closed forms: short pieces, one per workgroup, in dispatch order)
+            if (routes[i] != pg::PERM_ITEMS && routes[i] != pg::PERM_LADDER && pieces > 0x7fffffffull)
+                return fail(PG_ERR_INVALID_ARGUMENT, "segment too large for one launch");
+            switch (routes[i]) {
+            case pg::PERM_LADDER: {
                 const uint64_t lmost = pg::kPermLadderRows <= 2048 ? 0x7fffffffull : most;
-                if (pg::kPermLadderLds)
-                    PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_ladder_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)pg::kPermLadderLds));
-                // (rows that reference a witness from elsewhere read its Variable back: those waves wait for memory, and more of them resident
-                // hide it -- full residency for such segments)
-                const uint32_t lds = pg::ladder_foreign_per_item(s.wire_kind) ? 0u : pg::kPermLadderLds;
                 hipLaunchKernelGGL(pg::perm_ladder_kernel<false>, dim3((uint32_t)(pieces < lmost ? pieces : lmost)), dim3(pg::kThreads), lds,
                                    c->stream, X, s, Q, d_sigma);
-                continue;
+                break;
             }
-            if (template_seg(s)) {  // a small gadget's / gate batch's rows: sigma from the kind's wire table (perm_template_kernel)
-                const uint64_t pieces = pieces_of(s);
-                if (pieces > 0x7fffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "segment too large for one launch");
-                // (as for the ladders: four short-lived workgroups per CU where nothing is read back; full residency where the rows'
-                // Variables from elsewhere are -- those waves wait for memory)
-                const uint32_t lds = pg::template_foreign_per_item(s.wire_kind) ? 0u : pg::kPermLadderLds - 8192;
-                const pg::TemplateRows T = pg::template_rows(s.wire_kind);
-                if (s.row_off) {
-                    PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_template_kernel<true>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg::kPermLadderLds));
-                    hipLaunchKernelGGL(pg::perm_template_kernel<true>, dim3((uint32_t)pieces), dim3(pg::kThreads), lds, c->stream, X, s, T, Q, d_sigma);
-                } else {
-                    PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_template_kernel<false>),
-                                                   hipFuncAttributeMaxDynamicSharedMemorySize, (int)pg::kPermLadderLds));
-                    hipLaunchKernelGGL(pg::perm_template_kernel<false>, dim3((uint32_t)pieces), dim3(pg::kThreads), lds, c->stream, X, s, T, Q, d_sigma);
-                }
-                continue;
+            case pg::PERM_LADDER_RAGGED:
+                hipLaunchKernelGGL(pg::perm_ladder_kernel<true>, dim3((uint32_t)pieces), dim3(pg::kThreads), lds, c->stream, X, s, Q, d_sigma);
+                break;
+            case pg::PERM_TEMPLATE:
+                hipLaunchKernelGGL(pg::perm_template_kernel<false>, dim3((uint32_t)pieces), dim3(pg::kThreads), lds, c->stream, X, s,
+                                   pg::template_rows(s.wire_kind), Q, d_sigma);
+                break;
+            case pg::PERM_TEMPLATE_RAGGED:
+                hipLaunchKernelGGL(pg::perm_template_kernel<true>, dim3((uint32_t)pieces), dim3(pg::kThreads), lds, c->stream, X, s,
+                                   pg::template_rows(s.wire_kind), Q, d_sigma);
+                break;
+            case pg::PERM_ITEMS: {
+                const uint64_t groups = (s.items + s.group - 1) / s.group;
+                hipLaunchKernelGGL(pg::perm_item_kernel, dim3((uint32_t)(groups < most ? groups : most)), dim3(pg::kThreads), lds, c->stream, X, s,
+                                   groups, Q, d_sigma);
+                break;
             }
-            if (ragged_ladder(s)) {  // per-item bounds: the same closed form, the ladder length of an item from the call's prefix sums
-                const uint64_t pieces = pieces_of(s);
-                if (pieces > 0x7fffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "segment too large for one launch");
-                if (pg::kPermLadderLds)
-                    PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_ladder_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                   (int)pg::kPermLadderLds));
-                hipLaunchKernelGGL(pg::perm_ladder_kernel<true>, dim3((uint32_t)pieces), dim3(pg::kThreads), pg::kPermLadderLds, c->stream, X, s, Q,
-                                   d_sigma);
-                continue;
             }
-            hipLaunchKernelGGL(pg::perm_item_kernel, dim3((uint32_t)(groups < most ? groups : most)), dim3(pg::kThreads),
-                               pg::perm_local_lds_bytes(s.group * s.L, s.group * s.V) + PG_PERM_LDS_PAD, c->stream, X, s, groups, Q, d_sigma);
         }
         for (const auto &g : gaps) {
             const uint64_t nblk = (g.second - g.first + pg::kPermChunk - 1) / pg::kPermChunk;
@@ -1915,8 +1845,6 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
         // (every run is padded_n - n entries, give or take the odd one at either end: the same number of workgroups for each)
         const uint64_t per_run = ((padded_n - c->n) / 2 + 1 + pg::kPermIdentityUnits - 1) / pg::kPermIdentityUnits;
         if (4 * per_run > 0x7fffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "padding too large for one launch");
-        PG_HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(pg::perm_identity_kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                       (int)pg::kPermIdentityLds));  // (more dynamic LDS than the default limit; per device, cheap)
         hipLaunchKernelGGL(pg::perm_identity_kernel, dim3((uint32_t)(4 * per_run)), dim3(pg::kThreads), pg::kPermIdentityLds, c->stream,
                            d_sigma, c->n, padded_n);
     }

@@ -34,19 +34,10 @@ namespace pg {
 // and two per group (without its reads: 12.4-12.8 ms per 270 M rows, with them 15.2-15.7; the reads' share of the traffic is 1.2).
 // The loader's counter is its own.
 constexpr int kMatStoreThreads = PG_MAT_THREADS, kMatThreads = kMatStoreThreads + 64;
-constexpr uint32_t kMatWindowVars = 1040;  // two windows of 33 280 B: two workgroups per CU (fewer, fatter store streams: -3 %); range_check's 1034 Variables per item fit
+// (kMatWindowVars = 1040 Variables per LDS window: footprint.hpp)
 constexpr uint32_t kMatTailRows = 16;      // rows of the NEXT group that come along with a group's last line of w_4 (at most 15)
 
-// how the store waves learn a row's three Variables
-enum : int {
-    MAT_READ_WIRES = 0,  // from the wire columns (any batched call)
-    MAT_SELF = 2,        // in closed form (PermSeg::wire_kind = KIND, compiled in: one instantiation per kind keeps the wire functions
-                         // of the others -- and their registers -- out), and the store waves load NOTHING: the rows that come along
-                         // from the next group and the ONE Variable per item that may come from elsewhere (the witness of the
-                         // `_allocated` kinds and of scalar_decomposition) get their values from the loader; such groups have at most
-                         // kMatWitItems items
-};
-constexpr uint32_t kMatWitItems = 4;  // (these kinds create >= 257 Variables per item: a window holds at most four)
+// how the store waves learn a row's three Variables: MAT_READ_WIRES / MAT_SELF, and kMatWitItems = 4 -- footprint.hpp (mat_route picks the instantiation)
 
 // RAGGED (MAT_SELF, WIRES_MAX_BOUND only): per-item bounds -- rows and Variables by the call's prefix sums, the ladder length of an item
 // from its row count (L = 2 n + 5).  The loader reads the group's prefix sums and leaves them in LDS for the store waves.

@@ -28,43 +28,12 @@
 #include <rocprim/rocprim.hpp>
 
 #include "composer.hpp"
+#include "footprint.hpp"
 #include "range_gadgets.hpp"
 
 namespace pg {
 
-// footprint of a batched call: `items` items, each owning a run of rows and a run of Variables it created itself.
-// Uniform calls: L rows / V Variables per item.  Ragged calls (per-item public bounds, is_non_zero items that stop at
-// their error): row_off / var_off are the call's exclusive prefix sums (items + 1 entries, relative to the bases) and
-// L, V the largest item.  `group` consecutive items are linked by one workgroup as if they were one item.
-struct PermSeg {
-    uint64_t gate_base, gate_end, var_base, var_end;
-    uint32_t L, V;
-    uint64_t items;
-    const uint64_t *row_off, *var_off;
-    uint32_t group;
-    // The call's wires in closed form (0: not known -- read the wire columns): the ladder gadgets' rows reference the item's own
-    // Variables at offsets that are a function of the row and the ladder length alone (range_gadgets.hpp, bound_wire_offsets:
-    // what the emitter wrote them from), so whoever needs the Variables of a row -- the wire-value columns of
-    // pg_composer_materialize -- can compute them instead of reading 24 bytes per row back.
-    uint32_t wire_kind, wire_n;
-    // perm_ladder_kernel: the segment's slots on the sparse list -- ladder_foreign_per_item(wire_kind) per item, in closed form (set by
-    // pg_composer_permutation for the pass it launches)
-    uint64_t sparse_base;
-    // Rows behind every item's own that hold its RESULT Variable on all three wires (constrain_to_constant / boolean_gate on the result:
-    // the loop of the reference's tests, recorded call by call and flushed as one launch -- capi_composer.inc, flush): they count as
-    // the item's rows (L includes them), their wires and their place in the result's cycle are closed forms like the others.  Kinds that
-    // allocate their witness only.
-    uint32_t tail;
-    // perm_ladder_kernel<true> (per-item bounds): the item that holds the first row of every piece of kPermLadderRows rows (set by
-    // pg_composer_permutation for the pass it launches; perm_piece_items_kernel fills it from the call's prefix sums)
-    const uint32_t *piece_item;
-};
-enum : uint32_t { WIRES_UNKNOWN = 0, WIRES_RANGE_CHECK = 1, WIRES_MAX_BOUND = 2, WIRES_RANGE_CHECK_ALLOCATED = 3, WIRES_MAX_BOUND_ALLOCATED = 4,
-                  WIRES_DECOMPOSITION = 5,
-                  WIRES_MIX = 6,    // the fused scalar mix (ten rows, fifteen Variables: ScalarMixGD::row; eight / thirteen where v = 0)
-                  // the small gadgets on Variables from elsewhere (scalar_gadgets.hpp) and the gate batches (composer.hpp): SegTemplate below
-                  WIRES_SELECT_ZERO = 7, WIRES_SELECT_ONE = 8, WIRES_MAYBE_EQUAL = 9, WIRES_IS_NON_ZERO = 10, WIRES_GATE_OUT = 11,
-                  WIRES_GATE_ROWS = 12, WIRES_KINDS = 13 };
+// PermSeg -- the footprint of a batched call --, the WIRES_* kinds and which kernel links a footprint's rows (perm_route): footprint.hpp
 constexpr uint32_t kZeroWire = 0xfffffffeu;  // "zero_var" (the composer's Variable with value 0: is_non_zero's first row has it)
 // offsets (from the item's first own Variable) of the three wires of item-row j; kWitnessWire: the witness, which is the item's
 // first Variable for the kinds that allocate it and a Variable from elsewhere (read it from the wire column) for the others
@@ -72,6 +41,7 @@ __device__ __forceinline__ void seg_wire_offsets(uint32_t kind, uint32_t n, uint
     const uint32_t x0 = kind == WIRES_RANGE_CHECK || kind == WIRES_MAX_BOUND ? 1u : 0u;
     if (tail && kind >= WIRES_RANGE_CHECK && kind <= WIRES_MAX_BOUND_ALLOCATED) {
         // (PermSeg::tail) the rows behind the gadget's own: its result -- the item's last Variable -- three times
+        // (own = kind_rows(kind, n) and res = kind_vars(kind, n) - 1 of footprint.hpp's table, spelled out: this is device code)
         const bool rc = kind == WIRES_RANGE_CHECK || kind == WIRES_RANGE_CHECK_ALLOCATED;
         const uint32_t own = rc ? 4 * n + 11 : 2 * n + 5, res = x0 + (rc ? 2 * n + 522 : n + 260);
         if (j >= own) {
@@ -145,8 +115,6 @@ struct PermCtx {
 constexpr uint32_t kPermIters = 16;                               // gates per thread of the gap kernel
 constexpr uint64_t kPermChunk = (uint64_t)kThreads * kPermIters;  // gates per workgroup of the gap kernel
 constexpr uint32_t kPermRowsPerThread = 4;  // item kernel: rows loaded per thread before any is processed (5 spilled at the 72 registers seven workgroups per CU leave)
-constexpr uint32_t kPermLocalLdsLimit = 64 * 1024 - 256;
-constexpr uint32_t kPermNone = 0xFFFF, kPermDone = 0xFFFE;
 
 __device__ __forceinline__ uint64_t perm_encode(uint64_t gate, uint32_t wire, uint64_t padded_n) { return wire * padded_n + gate; }
 __device__ __forceinline__ uint64_t perm_encode_pos(uint64_t p, uint64_t padded_n) { return (p & 3) * padded_n + (p >> 2); }
@@ -245,9 +213,7 @@ __global__ __launch_bounds__(kThreads) void perm_gap_kernel(const PermCtx X, uin
 // lives on occupancy (halving the resident workgroups costs 1.7x): cnt[V] (u32, LDS atomics), off[V+1] (u16),
 // lw[3L] (u16: local Variable id per position, later reused for the successors of those positions), pos[3L] (u16),
 // sig4[L] (u16: successors of the fourth-wire positions), zm[L] (u8: wires holding zero_var | foreign wires << 4)
-__host__ __device__ inline uint32_t perm_local_lds_bytes(uint32_t L, uint32_t V) {
-    return 4 * V + 2 * (V + 2) + 2 * (3 * L + 3 * L + L) + L + 16;
-}
+// (perm_local_lds_bytes, footprint.hpp)
 
 __global__ __launch_bounds__(kThreads, 7) void perm_item_kernel(const PermCtx X, const PermSeg S, uint64_t groups, const PermSparse Q,
                                                             uint64_t *sigma) {
@@ -480,27 +446,18 @@ __device__ __forceinline__ uint32_t ladder_foreign_wires(uint32_t kind, uint32_t
 
 // positions of an item that hold a witness allocated elsewhere, and the rank of (item-row j, wire w) among them in recording order:
 // every item owns that many consecutive slots of the sparse list, so a lane knows where its entry goes without asking anybody
-__host__ __device__ inline uint32_t ladder_foreign_per_item(uint32_t kind) {
-    return kind == WIRES_RANGE_CHECK_ALLOCATED ? 4u : kind == WIRES_MAX_BOUND_ALLOCATED ? 2u : kind == WIRES_DECOMPOSITION ? 1u : 0u;
-}
+// (ladder_foreign_per_item: footprint.hpp)
 __device__ __forceinline__ uint32_t ladder_foreign_rank(uint32_t kind, uint32_t j, uint32_t w) {
     if (kind == WIRES_DECOMPOSITION) return 0u;
     return (j ? 2u : 0u) + w;  // rows 0 (and 2n + 5 of range_check): wires 0 and 1
 }
 
-#ifndef PG_PERM_LADDER_ROWS
-#define PG_PERM_LADDER_ROWS 512
-#endif
-#ifndef PG_PERM_LADDER_LDS
-#define PG_PERM_LADDER_LDS 39936
-#endif
 // Short-lived workgroups: ONE pass of 512 rows each (16 KiB written: 4 KiB of each of sigma's four columns), started in address order by
 // the dispatcher, four resident per CU (an unused dynamic LDS allocation bounds them) -- the same finding as perm_identity_kernel's: what is
 // under way at any moment should be a narrow window.  The whole call on a 270 M-row circuit, one process, same placement
 // (tools/perm_variants.py): pieces of 8192 rows walked by long-lived workgroups 3.77 ms; 512 rows, full residency 3.45; 512 rows, 4 per CU
 // 3.2; 3 per CU 3.55; 2 per CU 4.4 (too few waves for the arithmetic); 1024 rows, 4 per CU 3.26.
-constexpr uint32_t kPermLadderRows = PG_PERM_LADDER_ROWS;  // rows per workgroup piece (a multiple of 2 * kThreads)
-constexpr uint32_t kPermLadderLds = PG_PERM_LADDER_LDS;    // dynamic LDS per workgroup, unused: bounds how many are resident per CU
+// (kPermLadderRows = 512 rows per workgroup piece, kPermLadderLds = 39936 bytes of unused dynamic LDS: footprint.hpp)
 // RAGGED (max_bound with a bound per item, WIRES_MAX_BOUND: range.rs:82-113 with bound_i): an item's ladder length follows from its row
 // count, L_i = 2 n_i + 5, and its place from the call's prefix sums -- the piece's first item from S.piece_item, the <= 58 items a piece
 // of 512 rows can hold (an item has at least nine) from a window of the prefix sums in LDS that every lane searches (six steps).
@@ -698,12 +655,12 @@ constexpr SegTemplate kSegTemplates[WIRES_KINDS - WIRES_MIX] = {
 #undef PG_TF2
 #undef PG_TZ
 #undef PG_TX
-// positions of a full item that hold a Variable from elsewhere (= its slots on the sparse list; a short item leaves the rest as holes)
-__host__ __device__ inline uint32_t template_foreign_per_item(uint32_t kind) {
-    return kind == WIRES_SELECT_ZERO || kind == WIRES_MAYBE_EQUAL || kind == WIRES_IS_NON_ZERO || kind == WIRES_GATE_OUT ? 2u
-           : kind == WIRES_SELECT_ONE || kind == WIRES_GATE_ROWS ? 3u : 0u;
+// (template_foreign_per_item, is_template_kind: footprint.hpp -- as are the full items' rows and Variables, which the host goes by)
+constexpr bool seg_templates_match_kind_shapes(uint32_t k = WIRES_MIX) {
+    return k == WIRES_KINDS || (kSegTemplates[k - WIRES_MIX].L[0] == kind_rows(k) && kSegTemplates[k - WIRES_MIX].V[0] == kind_vars(k) &&
+                                seg_templates_match_kind_shapes(k + 1));
 }
-__host__ __device__ inline bool is_template_kind(uint32_t kind) { return kind >= WIRES_MIX && kind < WIRES_KINDS; }
+static_assert(seg_templates_match_kind_shapes(), "footprint.hpp's kKindShapes and kSegTemplates agree about a full item");
 
 // What the kernels take: the table and what follows from it, one 64-bit word per (shape, row) -- 16 bits per wire:
 //   bits 0-1  type   0 none, 1 an own Variable, 2 a Variable from elsewhere, 3 zero_var

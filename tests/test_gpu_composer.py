@@ -1219,3 +1219,36 @@ def test_ladder_sigma_closed_form_over_the_ladder_lengths(engine, bits):
         w, g = np.argwhere(got != exp)[0]
         raise AssertionError(f"sigma differs first at wire {w}, gate {g}: {got[w, g]} != {exp[w, g]} (n = {n1})")
     _sigma_properties(dev, padded)
+
+
+@pytest.mark.parametrize("bits", [0, 1])
+def test_sigma_of_ladders_too_short_for_the_closed_form(engine, bits):
+    """a scalar_decomposition of fewer than two bits has no ladder to speak of: its footprint is the one kind of batched append
+    that pg_composer_permutation still links with perm_item_kernel (csrc/footprint.hpp, perm_route: PERM_ITEMS) -- here more items
+    than one workgroup's group of them, on witnesses from elsewhere (one of them zero_var), with a result used by a later row and an
+    odd first row.  == the oracle's bookkeeping."""
+    from oracle import pyoracle as po
+    batch = 401
+    dev, ora = pg.StandardComposer(engine, 1 << 13, 1 << 17), po.Composer()
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to("cuda:0")
+    dev.boolean_gate(dev.add_witness_to_circuit_description(S(1)))
+    ora.L.composer_boolean_gate(ora.c, ora.L.composer_add_witness_to_circuit_description(ora.c, po.fr(synth.mont(1))))
+    wit = synth.scalars_from_ints([i % 3 for i in range(batch)])
+    first = dev.add_input_batch(t(wit))
+    allocs = [ora.allocate(w) for w in wit]
+    assert first == int(allocs[0].var)
+    wv_list = [first + i for i in range(batch)]
+    wv_list[7], wit[7] = 0, synth.scalars_from_ints([0])[0]  # zero_var as a witness
+    oallocs = [po.AllocatedScalar(v, po.fr(x)) for v, x in zip(wv_list, wit)]
+    r = dev.scalar_decomposition_batch(bits, torch.tensor(wv_list, dtype=torch.int64, device="cuda:0"), t(wit))
+    res = [int(ora.L.scalar_decomposition_gadget(ora.c, bits, a, None)) for a in oallocs]
+    assert list(r.cpu().numpy().view(np.uint64)) == res
+    dev.assert_equal(res[3], res[-1])
+    ora.L.composer_assert_equal(ora.c, res[3], res[-1])
+    same(dev, ora)
+    padded = 1 << (dev.circuit_size() - 1).bit_length()
+    got, exp = dev.permutation(padded).cpu().numpy().view(np.uint64), ora.sigma(padded)
+    if not np.array_equal(got, exp):
+        w, g = np.argwhere(got != exp)[0]
+        raise AssertionError(f"sigma differs first at wire {w}, gate {g}: {got[w, g]} != {exp[w, g]}")
+    _sigma_properties(dev, padded)
