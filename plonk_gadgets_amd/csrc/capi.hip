@@ -12,6 +12,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <initializer_list>
+#include <memory>
 #include <new>
 #include <functional>
 #include <string>
@@ -62,8 +63,10 @@ pg_status check_columns(const pg_columns *c) {
 struct pg_engine {
     int device = -1;
     int num_cus = 0;
-    uint4 *d_pow2 = nullptr;  // mont(2^i), i < 256
-    // Every Scratch below is grow-only and freed by its destructor (delete e, the engine's device current: pg_engine_destroy).
+    // Every member below that owns something (owners.hpp) is released by its destructor: delete e in pg_engine_destroy, which
+    // first makes the engine's device current and drains the side stream and the last copy out of `seg`.  After that no member
+    // depends on another, so their order says nothing about release.
+    Scratch d_pow2;  // mont(2^i), i < 256
     // scratch of the ragged plans: per-item counts (uint32_t), block sums (uint64_t), error counter (uint32_t)
     Scratch d_rows, d_vars, d_blk_rows, d_blk_vars;
     Scratch d_blk_agg;  // single-launch plans (emit.hpp, PlanScan): published block totals (unsigned long long); [blocks] = blocks done
@@ -71,18 +74,19 @@ struct pg_engine {
     uint64_t scratch_items = 0, scratch_blocks = 0;
     // totals of the last plan, written by async copies into pinned host memory (read after a synchronisation)
     using PlanResult = pg::PlanTotals;
-    PlanResult *h_plan = nullptr;
+    Pinned h_plan;
+    PlanResult *plan() const { return h_plan.as<PlanResult>(); }
     // scratch of the inversions: the pre-pass parks an element and its running product (64 B per element),
     // the fused mix one running product per item (32 B)
     Scratch d_prefix;
     uint64_t inv_elems = 0;
     // the pre-pass runs on its own stream beside the rows-only emit launch
-    hipStream_t side = nullptr;
-    hipEvent_t ev_fork = nullptr, ev_inv = nullptr;
+    Stream side;
+    Event ev_fork, ev_inv;
     // the stream the last call was issued on (see enter_stream)
     hipStream_t last_stream = nullptr;
     bool have_last = false;
-    hipEvent_t ev_switch = nullptr;
+    Event ev_switch;
     // scratch of pg_sigma_evaluations / pg_permutation_product: flags, omega tables, tile products, denominators
     Scratch d_pp;
     // scratch of pg_ntt: its omega and coset tables
@@ -93,10 +97,7 @@ struct pg_engine {
     Scratch d_msm, d_srs;
     // scratch of pg_msm_segmented: products, sums and segment offsets; the pinned buffer its offsets are staged in
     Scratch d_msm_small;
-    uint64_t *h_seg = nullptr;
-    uint64_t seg_cap = 0;
-    hipEvent_t ev_seg = nullptr;  // the last copy out of h_seg
-    bool seg_pending = false;
+    Staging seg;
     // scratch of pg_poly_open: its tile totals and carries
     Scratch d_open;
     // scratch of pg_plonk_sides: the decode status of every commitment, 11 bytes a proof
@@ -141,7 +142,7 @@ pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64
     P.blk_vars = e->d_blk_vars.as<uint64_t>();
     P.row_off = d_row_off;
     P.var_off = d_var_off;
-    P.host = e->h_plan;
+    P.host = e->plan();
     P.err_count = with_errs ? e->d_err_count.as<uint32_t>() : nullptr;
 #if defined(PG_PLAN_TWO_LAUNCHES)  // A/B build
     P.fused = 0;
@@ -152,12 +153,12 @@ pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64
 }
 
 pg_status plan_totals(pg_engine *e, uint64_t *n_rows, uint64_t *n_vars) {
-    if (e->h_plan->pad) {
-        e->h_plan->pad = 0;
+    if (e->plan()->pad) {
+        e->plan()->pad = 0;
         return fail(PG_ERR_HIP, "a plan's look-back gave up waiting for another block's totals");
     }
-    *n_rows = e->h_plan->n_gates;
-    *n_vars = e->h_plan->n_vars;
+    *n_rows = e->plan()->n_gates;
+    *n_vars = e->plan()->n_vars;
     return PG_OK;
 }
 
@@ -173,7 +174,7 @@ pg_status scan_counts(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_
                                e->d_blk_vars.as<uint64_t>(), nblk);
         hipLaunchKernelGGL(pg::scan_final_kernel, dim3(nblk), dim3(pg::kThreads), 0, st, e->d_rows.as<uint32_t>(),
                            e->d_vars.as<uint32_t>(), batch, e->d_blk_rows.as<uint64_t>(), e->d_blk_vars.as<uint64_t>(), d_row_off,
-                           d_var_off, prefixed, e->h_plan, with_errs ? e->d_err_count.as<uint32_t>() : nullptr);
+                           d_var_off, prefixed, e->plan(), with_errs ? e->d_err_count.as<uint32_t>() : nullptr);
         PG_HIP_TRY(hipGetLastError());
     }
     if (n_rows) {  // synchronous form
@@ -234,7 +235,7 @@ constexpr unsigned kOrderingEvent = hipEventDisableTiming | hipEventDisableSyste
 // otherwise have an event recorded on it that orders nothing.
 pg_status enter_stream(pg_engine *e, hipStream_t st) {
     PG_HIP_TRY(hipSetDevice(e->device));
-    if (e->have_last && e->last_stream != st) PG_HIP_TRY(hipStreamWaitEvent(st, e->ev_switch, 0));
+    if (e->have_last && e->last_stream != st) PG_HIP_TRY(hipStreamWaitEvent(st, e->ev_switch.get(), 0));
     e->last_stream = st;
     e->have_last = true;
     return PG_OK;
@@ -242,7 +243,7 @@ pg_status enter_stream(pg_engine *e, hipStream_t st) {
 struct StreamScope {  // declared right after enter_stream succeeds; its destructor runs on every way out of the call
     pg_engine *e;
     hipStream_t st;
-    ~StreamScope() { (void)hipEventRecord(e->ev_switch, st); }
+    ~StreamScope() { (void)hipEventRecord(e->ev_switch.get(), st); }
 };
 
 // Once a call has forked its pre-pass to the engine's side stream, the caller's stream waits for the side stream on EVERY way
@@ -254,8 +255,8 @@ struct SideJoin {
     bool forked = false, joined = false;
     ~SideJoin() {
         if (!forked || joined) return;
-        (void)hipEventRecord(e->ev_inv, e->side);
-        (void)hipStreamWaitEvent(st, e->ev_inv, 0);
+        (void)hipEventRecord(e->ev_inv.get(), e->side.get());
+        (void)hipStreamWaitEvent(st, e->ev_inv.get(), 0);
     }
 };
 
@@ -368,10 +369,10 @@ pg_status launch(pg_engine *e, const typename GD::Args &A, const pg_columns *c, 
             side = elems >= 2048 && elems < (1ull << 18);
             hipStream_t inv_st = st;
             if (side) {
-                PG_HIP_TRY(hipEventRecord(e->ev_fork, st));  // the pre-pass reads the call's inputs: order it after the stream
-                PG_HIP_TRY(hipStreamWaitEvent(e->side, e->ev_fork, 0));
+                PG_HIP_TRY(hipEventRecord(e->ev_fork.get(), st));  // the pre-pass reads the call's inputs: order it after the stream
+                PG_HIP_TRY(hipStreamWaitEvent(e->side.get(), e->ev_fork.get(), 0));
                 join.forked = true;
-                inv_st = e->side;
+                inv_st = e->side.get();
             }
             if constexpr (pg::InvDense<GD>::ok) {
                 O.inv_dense = e->d_prefix.as<uint4>();
@@ -381,7 +382,7 @@ pg_status launch(pg_engine *e, const typename GD::Args &A, const pg_columns *c, 
             hipLaunchKernelGGL((pg::batch_invert_kernel<GD, GRP>), dim3(blocks), dim3(pg::kThreads), 0, inv_st, A, O, elems,
                                (uint32_t)groups, e->d_prefix.as<uint4>());
             PG_HIP_TRY(hipGetLastError());
-            if (side) PG_HIP_TRY(hipEventRecord(e->ev_inv, e->side));
+            if (side) PG_HIP_TRY(hipEventRecord(e->ev_inv.get(), e->side.get()));
         }
         const uint32_t max_blocks = (uint32_t)e->num_cus * (values_only ? PG_GRID_BLOCKS_PER_CU : PG_EMIT_GRID_BLOCKS_PER_CU);
         const dim3 egrid(O.tiles < max_blocks ? O.tiles : max_blocks);
@@ -393,7 +394,7 @@ pg_status launch(pg_engine *e, const typename GD::Args &A, const pg_columns *c, 
         }
         PG_HIP_TRY(hipGetLastError());
         if (side) {
-            PG_HIP_TRY(hipStreamWaitEvent(st, e->ev_inv, 0));  // join
+            PG_HIP_TRY(hipStreamWaitEvent(st, e->ev_inv.get(), 0));  // join
             join.joined = true;
         }
         return PG_OK;
@@ -438,7 +439,7 @@ pg_status error_plan(pg_engine *e, PlanKernel kernel, const pg_scalar *d_value, 
     if (batch == 0) {  // stream-ordered like every other write of the plan result
         PG_TRY(enter_stream(e, static_cast<hipStream_t>(stream)));
         StreamScope scope{e, static_cast<hipStream_t>(stream)};
-        PG_HIP_TRY(hipMemsetAsync(e->h_plan, 0, sizeof(pg_engine::PlanResult), static_cast<hipStream_t>(stream)));
+        PG_HIP_TRY(hipMemsetAsync(e->plan(), 0, sizeof(pg_engine::PlanResult), static_cast<hipStream_t>(stream)));
         return PG_OK;
     }
     PG_TRY(check_scalars(d_value, "value array"));
@@ -456,7 +457,7 @@ pg_status error_plan(pg_engine *e, PlanKernel kernel, const pg_scalar *d_value, 
                        plan_scan(e, batch, d_row_off, d_var_off, true));
     PG_HIP_TRY(hipGetLastError());
     PG_TRY(scan_counts(e, batch, d_row_off, d_var_off, &out->n_gates, &out->n_vars, st, true));
-    const uint32_t errs = e->h_plan->errs;
+    const uint32_t errs = e->plan()->errs;
     if (err_count) *err_count = errs;
     if (errs) return fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(errs) + " item(s) have no inverse (value = 0)");
     return PG_OK;
@@ -494,19 +495,13 @@ pg_status pg_engine_create(int device, pg_engine **out) {
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0)
         return fail(PG_ERR_NO_DEVICE, std::string("device is ") + prop.gcnArchName + ", library is built for gfx950 only");
     PG_HIP_TRY(hipSetDevice(device));
-    pg_engine *e = new (std::nothrow) pg_engine();
+    std::unique_ptr<pg_engine> e(new (std::nothrow) pg_engine());
     if (!e) return fail(PG_ERR_HIP, "out of host memory");
     e->device = device;
     e->num_cus = prop.multiProcessorCount;
-    if (hipMalloc(&e->d_pow2, 256 * 2 * sizeof(uint4)) != hipSuccess) {
-        delete e;
-        return fail(PG_ERR_HIP, "hipMalloc(pow2 table) failed");
-    }
-    if (hipHostMalloc(reinterpret_cast<void **>(&e->h_plan), sizeof(pg_engine::PlanResult), hipHostMallocDefault) != hipSuccess) {
-        pg_engine_destroy(e);
-        return fail(PG_ERR_HIP, "hipHostMalloc(plan result) failed");
-    }
-    *e->h_plan = pg_engine::PlanResult{0, 0, 0, 0};
+    if (e->d_pow2.reserve(256 * 2 * sizeof(uint4)) != PG_OK) return fail(PG_ERR_HIP, "hipMalloc(pow2 table) failed");
+    if (e->h_plan.reserve(sizeof(pg_engine::PlanResult)) != PG_OK) return fail(PG_ERR_HIP, "hipHostMalloc(plan result) failed");
+    *e->plan() = pg_engine::PlanResult{0, 0, 0, 0};
     // the pre-pass is the critical path of a call with small items: highest priority, so its waves are placed ahead of
     // the rows-only emit launch it runs beside
     int prio_lo = 0, prio_hi = 0;
@@ -514,35 +509,23 @@ pg_status pg_engine_create(int device, pg_engine **out) {
 #if defined(PG_SIDE_STREAM_NORMAL_PRIORITY)
     prio_hi = 0;
 #endif
-    if (hipStreamCreateWithPriority(&e->side, hipStreamNonBlocking, prio_hi) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_fork, kOrderingEvent) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_inv, kOrderingEvent) != hipSuccess ||
-        hipEventCreateWithFlags(&e->ev_switch, kOrderingEvent) != hipSuccess) {
-        pg_engine_destroy(e);
+    if (e->side.create_with_priority(hipStreamNonBlocking, prio_hi) != PG_OK || e->ev_fork.create(kOrderingEvent) != PG_OK ||
+        e->ev_inv.create(kOrderingEvent) != PG_OK || e->ev_switch.create(kOrderingEvent) != PG_OK)
         return fail(PG_ERR_HIP, "creating the engine's side stream / events failed");
-    }
-    hipLaunchKernelGGL(pg::pow2_table_kernel, dim3(1), dim3(64), 0, nullptr, e->d_pow2);
+    hipLaunchKernelGGL(pg::pow2_table_kernel, dim3(1), dim3(64), 0, nullptr, e->d_pow2.as<uint4>());
     hipError_t err = hipDeviceSynchronize();
-    if (err != hipSuccess) {
-        pg_engine_destroy(e);
-        return fail(PG_ERR_HIP, std::string("pow2 table kernel: ") + hipGetErrorString(err));
-    }
-    *out = e;
+    if (err != hipSuccess) return fail(PG_ERR_HIP, std::string("pow2 table kernel: ") + hipGetErrorString(err));
+    *out = e.release();
     return PG_OK;
 }
 
+// ordering only: the engine's device current, the side stream and the last copy out of `seg` drained.  The members release themselves.
 void pg_engine_destroy(pg_engine *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
-    if (e->d_pow2) (void)hipFree(e->d_pow2);
-    if (e->ev_seg) { (void)hipEventSynchronize(e->ev_seg); (void)hipEventDestroy(e->ev_seg); }
-    if (e->h_seg) (void)hipHostFree(e->h_seg);
-    if (e->side) { (void)hipStreamSynchronize(e->side); (void)hipStreamDestroy(e->side); }
-    if (e->ev_fork) (void)hipEventDestroy(e->ev_fork);
-    if (e->ev_inv) (void)hipEventDestroy(e->ev_inv);
-    if (e->ev_switch) (void)hipEventDestroy(e->ev_switch);
-    if (e->h_plan) (void)hipHostFree(e->h_plan);
-    delete e;  // (every Scratch)
+    (void)hipStreamSynchronize(e->side.get());
+    (void)e->seg.wait();
+    delete e;
 }
 
 pg_status pg_engine_sync(pg_engine *e, void *stream) {
@@ -567,10 +550,10 @@ pg_status pg_scalars_from_canonical_batch(pg_engine *e, const void *d_bytes, uin
     hipLaunchKernelGGL(pg::from_canonical_kernel, dim3((uint32_t)((batch + pg::kThreads - 1) / pg::kThreads)), dim3(pg::kThreads), 0, st,
                        static_cast<const uint4 *>(d_bytes), batch, reinterpret_cast<uint4 *>(d_out), d_bad_mask, d_errs);
     PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(&e->h_plan->errs, d_errs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PG_HIP_TRY(hipMemcpyAsync(&e->plan()->errs, d_errs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PG_HIP_TRY(hipMemsetAsync(d_errs, 0, sizeof(uint32_t), st));  // zero between calls (see error_plan)
     PG_HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t bad = e->h_plan->errs;
+    const uint32_t bad = e->plan()->errs;
     if (bad_count) *bad_count = bad;
     if (bad) return fail(PG_ERR_BAD_ENCODING, std::to_string(bad) + " encoding(s) are not below the modulus");
     return PG_OK;
@@ -650,7 +633,7 @@ static pg_status range_check_common(pg_engine *e, const pg_scalar *min_range, co
     A.witness = reinterpret_cast<const uint4 *>(d_witness);
     A.witness_vars = d_witness_var;
     A.result_vars = d_result_vars;
-    A.pow2 = e->d_pow2;
+    A.pow2 = e->d_pow2.as<uint4>();
     return launch<pg::RangeCheckGD>(e, A, out, batch, gate_base, var_base, 0, nullptr, nullptr, stream, nullptr, values_only, stride_rows);
 }
 
@@ -685,7 +668,7 @@ pg_status pg_range_check_structure_batch(pg_engine *e, const pg_scalar *min_rang
     A.min_range = to_fr(min_range);
     A.max_range = to_fr(max_range);
     A.n = (uint32_t)lay.num_bits;
-    A.pow2 = e->d_pow2;
+    A.pow2 = e->d_pow2.as<uint4>();
     const pg::EmitOut O = make_out(&c, batch, pg::RangeCheckGD::W, gate_base, var_base, 0, nullptr, nullptr);
     const uint32_t max_blocks = (uint32_t)e->num_cus * PG_GRID_BLOCKS_PER_CU;
     hipLaunchKernelGGL((pg::emit_kernel<pg::RangeCheckGD, pg::EMIT_STRUCTURE>), dim3(grid_cap(O.tiles, max_blocks)), dim3(pg::kThreads), 0,
@@ -737,7 +720,7 @@ static pg_status decomposition_common(pg_engine *e, uint64_t num_bits, const pg_
     A.witness = reinterpret_cast<const uint4 *>(d_witness);
     A.witness_vars = d_witness_var;
     A.result_vars = d_result_vars;
-    A.pow2 = e->d_pow2;
+    A.pow2 = e->d_pow2.as<uint4>();
     return launch<pg::DecompositionGD>(e, A, out, batch, gate_base, var_base, 0, nullptr, nullptr, stream, nullptr, values_only);
 }
 
@@ -778,7 +761,7 @@ static pg_status max_bound_common(pg_engine *e, const pg_scalar *max_range, cons
     A.witness = reinterpret_cast<const uint4 *>(d_witness);
     A.witness_vars = d_witness_var;
     A.result_vars = d_result_vars;
-    A.pow2 = e->d_pow2;
+    A.pow2 = e->d_pow2.as<uint4>();
     return launch<pg::MaxBoundGD<false>>(e, A, out, batch, gate_base, var_base, 0, nullptr, nullptr, stream, nullptr, values_only, stride_rows);
 }
 
@@ -808,7 +791,7 @@ static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_m
     if (batch == 0) {
         PG_TRY(enter_stream(e, static_cast<hipStream_t>(stream)));
         StreamScope scope{e, static_cast<hipStream_t>(stream)};
-        PG_HIP_TRY(hipMemsetAsync(e->h_plan, 0, sizeof(pg_engine::PlanResult), static_cast<hipStream_t>(stream)));
+        PG_HIP_TRY(hipMemsetAsync(e->plan(), 0, sizeof(pg_engine::PlanResult), static_cast<hipStream_t>(stream)));
         return PG_OK;
     }
     PG_TRY(check_scalars(d_max_range, "d_max_range"));
@@ -821,7 +804,7 @@ static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_m
     StreamScope scope{e, st};
     const uint32_t grid = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
     hipLaunchKernelGGL(pg::max_bound_plan_kernel, dim3(grid), dim3(pg::kThreads), 0, st,
-                       reinterpret_cast<const uint4 *>(d_max_range), batch, e->d_pow2, d_num_bits, e->d_rows.as<uint32_t>(),
+                       reinterpret_cast<const uint4 *>(d_max_range), batch, e->d_pow2.as<uint4>(), d_num_bits, e->d_rows.as<uint32_t>(),
                        e->d_vars.as<uint32_t>(), plan_scan(e, batch, d_row_off, d_var_off, false));
     PG_HIP_TRY(hipGetLastError());
     // a max_bound plan has no failing items: the scan writes errs = 0 with the totals, in stream order
@@ -845,8 +828,8 @@ pg_status pg_plan_result(pg_engine *e, pg_layout *out, uint64_t *err_count) {
     if (!e || !out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     std::memset(out, 0, sizeof *out);
     PG_TRY(plan_totals(e, &out->n_gates, &out->n_vars));
-    if (err_count) *err_count = e->h_plan->errs;
-    return e->h_plan->errs ? fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(e->h_plan->errs) + " item(s) have no inverse")
+    if (err_count) *err_count = e->plan()->errs;
+    return e->plan()->errs ? fail(PG_ERR_NON_EXISTING_INVERSE, std::to_string(e->plan()->errs) + " item(s) have no inverse")
                            : PG_OK;
 }
 
@@ -868,7 +851,7 @@ static pg_status max_bound_ragged_common(pg_engine *e, const pg_scalar *d_max_ra
     A.num_bits_v = d_num_bits;
     A.witness = reinterpret_cast<const uint4 *>(d_witness);
     A.result_vars = d_result_vars;
-    A.pow2 = e->d_pow2;
+    A.pow2 = e->d_pow2.as<uint4>();
     return launch<pg::MaxBoundGD<true>>(e, A, out, batch, gate_base, var_base, 0, d_row_off, d_var_off, stream, nullptr, values_only);
 }
 
@@ -1025,7 +1008,7 @@ static pg_status scalar_mix_planned_common(pg_engine *e, const pg_scalar *d_v, c
     P.row_off = d_row_off;
     P.var_off = d_var_off;
     P.err_mask = d_err_mask;
-    P.host = e->h_plan;
+    P.host = e->plan();
     return launch<pg::ScalarMixGD>(e, A, out, batch, gate_base, var_base, zero_var, d_row_off, d_var_off, stream, &P, values_only);
 }
 

@@ -1,11 +1,24 @@
 // capi_composer.inc -- pg_composer (included by capi.hip inside its translation unit).
 
+// device arrays a ragged call plans into and, once its rows are emitted, the composer keeps for its footprint (words: uint64_t;
+// num_bits: uint32_t, calls with per-item bounds only)
+struct RaggedBuffers {
+    Scratch row_off, var_off, num_bits;
+    uint64_t *rows() const { return row_off.as<uint64_t>(); }
+    uint64_t *vars() const { return var_off.as<uint64_t>(); }
+    uint32_t *bits() const { return num_bits.as<uint32_t>(); }
+};
+
+// Everything the composer owns is a member that releases itself (owners.hpp): pg_composer_destroy makes the engine's device
+// current, drains the stream and deletes.  After that no member depends on another, so their order says nothing about release.
 struct pg_composer {
     pg_engine *e = nullptr;
     hipStream_t stream = nullptr;
-    uint64_t gate_cap = 0, var_cap = 0, n = 0, nvars = 0, zero_var = 0;
-    pg::ComposerCols cols{};
-    uint64_t *d_stage = nullptr;  // 40 words: inputs of single-gadget calls
+    uint64_t n = 0, nvars = 0, zero_var = 0;
+    // the nine columns: separate arrays, or ONE block with the selector columns a stride apart (pg_composer_spread_columns)
+    ColumnStore cols;
+    Scratch d_stage;  // 40 words: inputs of single-gadget calls
+    uint64_t *stage_words() const { return d_stage.as<uint64_t>(); }
     // public_inputs_sparse_store and the rows with a live fourth wire (host copies; uploaded by check/materialize)
     std::vector<uint64_t> pi_gate;
     std::vector<pg_scalar> pi_val;
@@ -14,15 +27,13 @@ struct pg_composer {
     std::vector<pg::PermSeg> segs;
     Scratch perm_small, perm_big, val_ws;  // val_ws: gathered assignments of batched calls
     Scratch perm_pieces;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
-    std::vector<void *> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
-    uint64_t *h_total = nullptr;  // pinned
+    std::vector<RaggedBuffers> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
+    Pinned h_total;  // 4 words: what a call reads back (made by pg_composer_create)
+    uint64_t *totals() const { return h_total.as<uint64_t>(); }
     uint64_t perm_last_sparse = 0;  // size of the sparse list the last permutation needed
     uint64_t sparse_hint = 0;       // wire positions the batched calls so far are expected to put on that list
     uint64_t sparse_cap_first = 0;  // pg_composer_permutation_reserve: first-pass size of that list (0: estimate)
     bool auto_grow = false;
-    // pg_composer_spread_columns: the nine arrays are parts of ONE allocation (block), the selector columns col_stride bytes apart
-    uint64_t col_stride = 0;
-    void *block = nullptr;
     // ---- the command queue (single composer calls are recorded on the host and flushed as few launches) ----
     struct Queued {
         uint8_t kind;        // 0: a gate call (g); 1: range_check; 2: max_bound -- on an allocated witness
@@ -44,11 +55,7 @@ struct pg_composer {
     // staging of a flush: pinned host memory and its device twin (grow-only), carved up run by run, so that the uploads
     // are truly asynchronous.  TWO such pairs take turns: a flush waits for the flush before the last one (the event recorded
     // at its end) before refilling that pair, not for the one the device may still be working on.
-    struct Staging {
-        char *h = nullptr, *d = nullptr;
-        size_t bytes = 0;
-        hipEvent_t ev = nullptr;
-    } staging[2];
+    Staging staging[2];
     int stage = 0;  // the pair the current flush fills
     size_t queue_used = 0;
     uint64_t flushes = 0, flush_launches = 0;  // statistics (pg_composer_queue_stats)
@@ -74,19 +81,6 @@ struct pg_composer {
 };
 
 namespace {
-
-// device buffers that live for one call: released on every way out (after the stream has drained: work may still read them)
-struct CallBuffers {
-    hipStream_t stream;
-    std::vector<void *> p;
-    explicit CallBuffers(hipStream_t st) : stream(st) {}
-    void own(void *q) { if (q) p.push_back(q); }
-    ~CallBuffers() {
-        if (p.empty()) return;
-        (void)hipStreamSynchronize(stream);
-        for (void *q : p) (void)hipFree(q);
-    }
-};
 
 pg_status flush(pg_composer *c);  // the command queue (below)
 
@@ -154,102 +148,22 @@ pg_composer::Sig gadget_sig(const pg_composer *c, uint64_t kind, const pg::Fr &b
     return h.done();
 }
 
-// new buffers for the live columns; the live part is copied on the composer's stream, the old buffers are released once that
-// copy is done.  Separate allocations (the default): only the arrays whose capacity grows move.  One block
-// (pg_composer_spread_columns): a new block laid out by pg_columns_slab_layout, all nine arrays move.  `rehome`: move although
-// nothing grows (the layout changed).
-pg_status grow(pg_composer *c, uint64_t gate_cap, uint64_t var_cap, bool rehome = false) {
-    if (gate_cap < c->gate_cap) gate_cap = c->gate_cap;
-    if (var_cap < c->var_cap) var_cap = c->var_cap;
-    if (!rehome && gate_cap == c->gate_cap && var_cap == c->var_cap) return PG_OK;
+// new arrays for the live columns in the layout `stride` asks for (ColumnStore::grow: the composer is untouched when it fails)
+pg_status grow(pg_composer *c, uint64_t gate_cap, uint64_t var_cap, uint64_t stride) {
+    if (stride == c->cols.stride() && gate_cap <= c->cols.gate_cap() && var_cap <= c->cols.var_cap()) return PG_OK;
     PG_HIP_TRY(hipSetDevice(c->e->device));
     PG_TRY(flush(c));  // queued calls land in the buffers they were recorded against
-    const bool one_block = c->col_stride != 0;
-    const bool move_rows = rehome || one_block || gate_cap > c->gate_cap, move_vars = rehome || one_block || var_cap > c->var_cap;
-    pg::ComposerCols nc = c->cols;
-    std::vector<void *> fresh;
-    bool ok = true;
-    auto take = [&](auto *&slot, uint64_t bytes) {
-        void *p = nullptr;
-        ok = ok && hipMalloc(&p, bytes) == hipSuccess;
-        if (ok) { slot = static_cast<std::remove_reference_t<decltype(slot)>>(p); fresh.push_back(p); }
-    };
-    void *new_block = nullptr;
-    if (one_block) {
-        uint64_t off[9], total = 0;
-        PG_TRY(pg_columns_slab_layout(gate_cap, var_cap, c->col_stride, off, &total));
-        // a block moves as a whole: the old one and the new one are alive together until the copy is done -- said before the
-        // allocation is tried, with the figures, rather than as a bare out-of-memory afterwards
-        size_t free_b = 0, total_b = 0;
-        if (hipMemGetInfo(&free_b, &total_b) == hipSuccess && total > free_b)
-            return fail(PG_ERR_CAPACITY, "composer with spread columns cannot grow to " + std::to_string(gate_cap) + " rows / " +
-                                             std::to_string(var_cap) + " variables: the new block of " + std::to_string(total >> 20) +
-                                             " MiB (selector columns " + std::to_string(c->col_stride >> 20) +
-                                             " MiB apart) must exist beside the old one during the move, and " +
-                                             std::to_string(free_b >> 20) + " MiB of device memory are free; reserve the final "
-                                             "capacity before pg_composer_spread_columns, or use a smaller stride");
-        ok = hipMalloc(&new_block, total) == hipSuccess;
-        if (ok) {
-            fresh.push_back(new_block);
-            uint8_t *b8 = static_cast<uint8_t *>(new_block);
-            for (int i = 0; i < 5; i++) nc.q[i] = reinterpret_cast<uint4 *>(b8 + off[i]);
-            for (int i = 0; i < 3; i++) nc.w[i] = reinterpret_cast<uint64_t *>(b8 + off[5 + i]);
-            nc.vars = reinterpret_cast<uint4 *>(b8 + off[8]);
-        }
-    } else {
-        if (move_rows) {
-            for (int i = 0; i < 5; i++) take(nc.q[i], gate_cap * 32);
-            for (int i = 0; i < 3; i++) take(nc.w[i], gate_cap * 8);
-        }
-        if (move_vars) take(nc.vars, var_cap * 32);
-    }
-    if (!ok) {
-        for (void *p : fresh) (void)hipFree(p);
-        (void)hipGetLastError();
-        return fail(PG_ERR_CAPACITY, "composer cannot grow to " + std::to_string(gate_cap) + " rows / " + std::to_string(var_cap) +
-                                         " variables: out of device memory");
-    }
-    std::vector<void *> old;
-    hipError_t err = hipSuccess;
-    auto copy = [&](void *dst, const void *src, uint64_t bytes) {
-        if (err == hipSuccess && bytes) err = hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream);
-    };
     // (a witness refresh under way: the rows of the previous build beyond the composer's end are still wanted)
-    const uint64_t live_rows = c->refill && c->old_n > c->n ? (c->old_n < c->gate_cap ? c->old_n : c->gate_cap) : c->n;
-    if (move_rows) {
-        for (int i = 0; i < 5; i++) {
-            copy(nc.q[i], c->cols.q[i], live_rows * 32);
-            if (!c->block) old.push_back(c->cols.q[i]);
-        }
-        for (int i = 0; i < 3; i++) {
-            copy(nc.w[i], c->cols.w[i], live_rows * 8);
-            if (!c->block) old.push_back(c->cols.w[i]);
-        }
-    }
-    if (move_vars) {
-        copy(nc.vars, c->cols.vars, c->nvars * 32);
-        if (!c->block) old.push_back(c->cols.vars);
-    }
-    if (c->block && (move_rows || move_vars)) old.push_back(c->block);  // (in one block everything moves together)
-    if (err == hipSuccess) err = hipStreamSynchronize(c->stream);
-    if (err != hipSuccess) {  // the composer keeps its old buffers
-        (void)hipStreamSynchronize(c->stream);
-        for (void *p : fresh) (void)hipFree(p);
-        return fail(PG_ERR_HIP, std::string("growing the composer: ") + hipGetErrorString(err));
-    }
-    for (void *p : old) (void)hipFree(p);
-    c->cols = nc;
-    c->block = new_block;
-    c->gate_cap = gate_cap;
-    c->var_cap = var_cap;
-    return PG_OK;
+    const uint64_t cap = c->cols.gate_cap(), live_rows = c->refill && c->old_n > c->n ? (c->old_n < cap ? c->old_n : cap) : c->n;
+    return c->cols.grow(gate_cap, var_cap, stride, live_rows, c->nvars, c->stream);
 }
+pg_status grow(pg_composer *c, uint64_t gate_cap, uint64_t var_cap) { return grow(c, gate_cap, var_cap, c->cols.stride()); }
 
 pg_status need(pg_composer *c, uint64_t rows, uint64_t vars) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    if (c->n + rows > c->gate_cap || c->nvars + vars > c->var_cap) {
+    if (c->n + rows > c->cols.gate_cap() || c->nvars + vars > c->cols.var_cap()) {
         if (c->auto_grow) {
-            uint64_t g = c->gate_cap, v = c->var_cap;
+            uint64_t g = c->cols.gate_cap(), v = c->cols.var_cap();
             if (c->n + rows > g) g = c->n + rows > 2 * g ? c->n + rows : 2 * g;
             if (c->nvars + vars > v) v = c->nvars + vars > 2 * v ? c->nvars + vars : 2 * v;
             return grow(c, g, v);
@@ -275,8 +189,7 @@ pg_status check_var_arrays(pg_composer *c, std::initializer_list<const pg_variab
     if (digest) *digest = pg_composer::Sig{0, 0};
     if (batch == 0) return PG_OK;
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    if (!c->h_total) PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_total), 32, hipHostMallocDefault));
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->d_stage + 37);  // the staging blob's last three words
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);  // the staging blob's last three words
     PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
     const uint64_t want = (batch + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
     unsigned long long salt = 0x243f6a8885a308d3ull;
@@ -287,12 +200,12 @@ pg_status check_var_arrays(pg_composer *c, std::initializer_list<const pg_variab
                            d_out, salt);
     }
     PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->h_total, d_out, 24, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->h_total[0] >= c->nvars)
-        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(c->h_total[0]) + " in a batched append (the composer has " +
+    if (c->totals()[0] >= c->nvars)
+        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(c->totals()[0]) + " in a batched append (the composer has " +
                                                  std::to_string(c->nvars) + ")");
-    if (digest) *digest = pg_composer::Sig{c->h_total[1], c->h_total[2]};
+    if (digest) *digest = pg_composer::Sig{c->totals()[1], c->totals()[2]};
     return PG_OK;
 }
 // the same digest of a device array of scalars (per-item public bounds): n * 4 words
@@ -300,30 +213,30 @@ pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_comp
     *digest = pg_composer::Sig{0, 0};
     if (n == 0) return PG_OK;
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    if (!c->h_total) PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_total), 32, hipHostMallocDefault));
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->d_stage + 37);
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);
     PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
     const uint64_t words = 4 * n, want = (words + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
     hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream,
                        reinterpret_cast<const uint64_t *>(d), words, d_out, 0x13198a2e03707344ull);
     PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->h_total, d_out, 24, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    *digest = pg_composer::Sig{c->h_total[1], c->h_total[2]};
+    *digest = pg_composer::Sig{c->totals()[1], c->totals()[2]};
     return PG_OK;
 }
 
 pg_columns cols_at(const pg_composer *c, uint64_t gate, uint64_t var) {
+    const pg::ComposerCols &v = c->cols.view();
     pg_columns o;
-    o.q_m = reinterpret_cast<pg_scalar *>(c->cols.q[0]) + gate;
-    o.q_l = reinterpret_cast<pg_scalar *>(c->cols.q[1]) + gate;
-    o.q_r = reinterpret_cast<pg_scalar *>(c->cols.q[2]) + gate;
-    o.q_o = reinterpret_cast<pg_scalar *>(c->cols.q[3]) + gate;
-    o.q_c = reinterpret_cast<pg_scalar *>(c->cols.q[4]) + gate;
-    o.w_l = c->cols.w[0] + gate;
-    o.w_r = c->cols.w[1] + gate;
-    o.w_o = c->cols.w[2] + gate;
-    o.var_values = reinterpret_cast<pg_scalar *>(c->cols.vars) + var;
+    o.q_m = reinterpret_cast<pg_scalar *>(v.q[0]) + gate;
+    o.q_l = reinterpret_cast<pg_scalar *>(v.q[1]) + gate;
+    o.q_r = reinterpret_cast<pg_scalar *>(v.q[2]) + gate;
+    o.q_o = reinterpret_cast<pg_scalar *>(v.q[3]) + gate;
+    o.q_c = reinterpret_cast<pg_scalar *>(v.q[4]) + gate;
+    o.w_l = v.w[0] + gate;
+    o.w_r = v.w[1] + gate;
+    o.w_o = v.w[2] + gate;
+    o.var_values = reinterpret_cast<pg_scalar *>(v.vars) + var;
     return o;
 }
 
@@ -331,41 +244,27 @@ pg_columns cols_at(const pg_composer *c, uint64_t gate, uint64_t var) {
 #define PG_QUEUE_MAX 8192  // entries; a full queue flushes itself
 #endif
 
-// a staging pair of at least `want` bytes; whatever used it last has left the device (its event) before it is replaced
-pg_status staging_reserve(pg_composer::Staging &S, size_t want) {
-    if (!S.ev) PG_HIP_TRY(hipEventCreateWithFlags(&S.ev, hipEventDisableTiming));
-    PG_HIP_TRY(hipEventSynchronize(S.ev));  // (never recorded: returns at once)
-    if (want <= S.bytes) return PG_OK;
-    if (S.h) (void)hipHostFree(S.h);
-    if (S.d) (void)hipFree(S.d);
-    S.h = S.d = nullptr;
-    S.bytes = 0;
-    PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&S.h), want, hipHostMallocDefault));
-    PG_HIP_TRY(hipMalloc(reinterpret_cast<void **>(&S.d), want));
-    S.bytes = want;
-    return PG_OK;
-}
 // room for one flush of n entries in the next staging pair; waits until the flush that last used it has left the device
 pg_status queue_begin(pg_composer *c, size_t n) {
     const size_t bytes = n * sizeof(pg::GateCmd) + (n + 8) * 64;  // every entry at most one GateCmd, plus alignment slack per run
     c->stage ^= 1;
-    pg_composer::Staging &S = c->staging[c->stage];
-    if (bytes > S.bytes) {  // both pairs grow together: the allocations (a millisecond each) fall into ONE flush
+    Staging &S = c->staging[c->stage];
+    if (bytes > S.size()) {  // both pairs grow together: the allocations (a millisecond each) fall into ONE flush
         const size_t want = bytes < (1u << 20) ? (1u << 20) : bytes * 2;
-        PG_TRY(staging_reserve(c->staging[c->stage ^ 1], want));
-        PG_TRY(staging_reserve(S, want));
+        PG_TRY(c->staging[c->stage ^ 1].acquire(want, true));
+        PG_TRY(S.acquire(want, true));
     } else {
-        PG_TRY(staging_reserve(S, 0));
+        PG_TRY(S.acquire(0, true));
     }
     c->queue_used = 0;
     return PG_OK;
 }
 // the next `bytes` of the staging pair (64-byte aligned): *h to fill, *d for the kernel
 void queue_slice(pg_composer *c, size_t bytes, char **h, char **d) {
-    pg_composer::Staging &S = c->staging[c->stage];
+    const Staging &S = c->staging[c->stage];
     c->queue_used = (c->queue_used + 63) & ~(size_t)63;
-    *h = S.h + c->queue_used;
-    *d = S.d + c->queue_used;
+    *h = S.host() + c->queue_used;
+    *d = S.device() + c->queue_used;
     c->queue_used += bytes;
 }
 
@@ -404,7 +303,7 @@ pg_status flush_gate_list(pg_composer *c, const std::vector<size_t> &at) {
         }
         PG_HIP_TRY(hipMemcpyAsync(d, h, n * sizeof(pg::GateCmd), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(pg::gate_queue_kernel, dim3(1), dim3(1024), 0, c->stream, reinterpret_cast<const pg::GateCmd *>(d), (uint32_t)n,
-                           first_var, max_level, c->cols);
+                           first_var, max_level, c->cols.view());
         PG_HIP_TRY(hipGetLastError());
         c->flush_launches++;
         i += n;
@@ -591,7 +490,7 @@ pg_status flush(pg_composer *c) {
     }
     c->queue.clear();
     c->flushes++;
-    if (hipEventRecord(c->staging[c->stage].ev, c->stream) != hipSuccess && st == PG_OK) st = fail(PG_ERR_HIP, "recording the flush's event failed");
+    if (c->staging[c->stage].sent(c->stream) != hipSuccess && st == PG_OK) st = fail(PG_ERR_HIP, "recording the flush's event failed");
     return st;
 }
 
@@ -613,7 +512,7 @@ pg_status run_gate(pg_composer *c, const pg::GateCmd &cmd_in) {
     }
     if (sa.in_place) cmd.op |= pg::OP_ROW_IN_PLACE;
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    hipLaunchKernelGGL(pg::gate_kernel, dim3(1), dim3(64), 0, c->stream, cmd, c->cols);
+    hipLaunchKernelGGL(pg::gate_kernel, dim3(1), dim3(64), 0, c->stream, cmd, c->cols.view());
     PG_HIP_TRY(hipGetLastError());
     sa.commit();
     return PG_OK;
@@ -641,7 +540,7 @@ pg_status push_row(pg_composer *c, pg_variable a, pg_variable b, pg_variable o, 
 }
 
 pg_status stage(pg_composer *c, const pg::StageBlob &blob, uint32_t words) {
-    hipLaunchKernelGGL(pg::stage_kernel, dim3(1), dim3(64), 0, c->stream, blob, c->d_stage, words);
+    hipLaunchKernelGGL(pg::stage_kernel, dim3(1), dim3(64), 0, c->stream, blob, c->stage_words(), words);
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
 }
@@ -659,21 +558,15 @@ pg_status pg_composer_create(pg_engine *e, uint64_t gate_capacity, uint64_t var_
     *out = nullptr;
     if (gate_capacity < 3 || var_capacity < 5) return fail(PG_ERR_INVALID_ARGUMENT, "capacity below the initial state");
     PG_HIP_TRY(hipSetDevice(e->device));
-    pg_composer *c = new (std::nothrow) pg_composer();
+    // (on every failing way out: pg_composer_destroy, which drains the stream before the members go)
+    std::unique_ptr<pg_composer, void (*)(pg_composer *)> owner(new (std::nothrow) pg_composer(), pg_composer_destroy);
+    pg_composer *c = owner.get();
     if (!c) return fail(PG_ERR_HIP, "out of host memory");
     c->e = e;
     c->stream = static_cast<hipStream_t>(stream);
-    c->gate_cap = gate_capacity;
-    c->var_cap = var_capacity;
-    bool ok = true;
-    for (int i = 0; i < 5; i++) ok = ok && hipMalloc(&c->cols.q[i], gate_capacity * 32) == hipSuccess;
-    for (int i = 0; i < 3; i++) ok = ok && hipMalloc(&c->cols.w[i], gate_capacity * 8) == hipSuccess;
-    ok = ok && hipMalloc(&c->cols.vars, var_capacity * 32) == hipSuccess;
-    ok = ok && hipMalloc(&c->d_stage, sizeof(pg::StageBlob)) == hipSuccess;
-    if (!ok) {
-        pg_composer_destroy(c);
+    if (c->cols.create(gate_capacity, var_capacity) != PG_OK || c->d_stage.reserve(sizeof(pg::StageBlob)) != PG_OK)
         return fail(PG_ERR_HIP, "hipMalloc of the composer columns failed");
-    }
+    PG_TRY(c->h_total.reserve(32));
     // StandardComposer::new(): zero_var = add_witness_to_circuit_description(0), then add_dummy_constraints()
     pg_scalar zero, s;
     from_fr(pg::fr_zero(), &zero);
@@ -694,16 +587,13 @@ pg_status pg_composer_create(pg_engine *e, uint64_t gate_capacity, uint64_t var_
             st = push_row(c, m20, six, seven, pg::fr_from_u64(1), pg::fr_from_u64(1), pg::fr_from_u64(1), pg::fr_from_u64(1),
                           pg::fr_from_u64(127), nullptr);
     }
-    if (st != PG_OK) {
-        pg_composer_destroy(c);
-        return st;
-    }
+    if (st != PG_OK) return st;
     c->n0 = c->n;
     c->nvars0 = c->nvars;
     c->log0 = c->log.size();
     c->fourth0 = c->fourth.size();
     c->rows_rewritten = 0;
-    *out = c;
+    *out = owner.release();
     return PG_OK;
 }
 
@@ -717,7 +607,6 @@ pg_status pg_composer_clear_witness(pg_composer *c) {
     PG_HIP_TRY(hipSetDevice(c->e->device));
     if (!c->ragged.empty()) {  // the prefix sums of ragged calls, referenced by the footprints that go now
         PG_HIP_TRY(hipStreamSynchronize(c->stream));
-        for (void *p : c->ragged) (void)hipFree(p);
         c->ragged.clear();
     }
     if (!c->refill || c->n > c->old_n) c->old_n = c->n;  // (a refresh that stopped early leaves the rest of the older build in place)
@@ -743,26 +632,12 @@ pg_status pg_composer_refresh_stats(const pg_composer *c, uint64_t *rows_in_plac
     return PG_OK;
 }
 
+// ordering only: the engine's device current, the composer's stream drained.  The members release themselves.
 void pg_composer_destroy(pg_composer *c) {
     if (!c) return;
     (void)hipSetDevice(c->e->device);
     (void)hipStreamSynchronize(c->stream);
-    if (c->block) {
-        (void)hipFree(c->block);
-    } else {
-        for (int i = 0; i < 5; i++) if (c->cols.q[i]) (void)hipFree(c->cols.q[i]);
-        for (int i = 0; i < 3; i++) if (c->cols.w[i]) (void)hipFree(c->cols.w[i]);
-        if (c->cols.vars) (void)hipFree(c->cols.vars);
-    }
-    if (c->d_stage) (void)hipFree(c->d_stage);
-    for (pg_composer::Staging &S : c->staging) {
-        if (S.d) (void)hipFree(S.d);
-        if (S.h) (void)hipHostFree(S.h);
-        if (S.ev) (void)hipEventDestroy(S.ev);
-    }
-    for (void *p : c->ragged) (void)hipFree(p);
-    if (c->h_total) (void)hipHostFree(c->h_total);
-    delete c;  // (every Scratch)
+    delete c;
 }
 
 uint64_t pg_composer_circuit_size(const pg_composer *c) { return c ? c->n : 0; }
@@ -783,20 +658,15 @@ pg_status pg_composer_reserve(pg_composer *c, uint64_t gate_capacity, uint64_t v
 pg_status pg_composer_spread_columns(pg_composer *c, uint64_t stride_bytes) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     if (stride_bytes > (1ull << 44)) return fail(PG_ERR_INVALID_ARGUMENT, "stride too large");
-    if (stride_bytes == c->col_stride) return PG_OK;
-    const uint64_t before = c->col_stride;
-    c->col_stride = stride_bytes;
-    const pg_status st = grow(c, c->gate_cap, c->var_cap, true);
-    if (st != PG_OK) c->col_stride = before;  // (the composer keeps its buffers and its layout)
-    return st;
+    return grow(c, 0, 0, stride_bytes);  // (when it fails the composer keeps its buffers and its layout)
 }
 pg_status pg_composer_auto_grow(pg_composer *c, int on) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     c->auto_grow = on != 0;
     return PG_OK;
 }
-uint64_t pg_composer_gate_capacity(const pg_composer *c) { return c ? c->gate_cap : 0; }
-uint64_t pg_composer_var_capacity(const pg_composer *c) { return c ? c->var_cap : 0; }
+uint64_t pg_composer_gate_capacity(const pg_composer *c) { return c ? c->cols.gate_cap() : 0; }
+uint64_t pg_composer_var_capacity(const pg_composer *c) { return c ? c->cols.var_cap() : 0; }
 
 pg_status pg_composer_queue(pg_composer *c, int on) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
@@ -959,9 +829,9 @@ pg_status pg_range_check(pg_composer *c, const pg_scalar *min_range, const pg_sc
         A.min_range = to_fr(min_range);
         A.max_range = to_fr(max_range);
         A.n = (uint32_t)lay.num_bits;
-        A.witness = reinterpret_cast<const uint4 *>(c->d_stage);
-        A.witness_vars = c->d_stage + 4;
-        A.pow2 = c->e->d_pow2;
+        A.witness = reinterpret_cast<const uint4 *>(c->stage_words());
+        A.witness_vars = c->stage_words() + 4;
+        A.pow2 = c->e->d_pow2.as<uint4>();
         const pg_columns at = cols_at(c, c->n, c->nvars);
         PG_TRY(launch<pg::RangeCheckGD>(c->e, A, &at, 1, c->n, c->nvars, c->zero_var, nullptr, nullptr, c->stream, nullptr, sa.in_place));
     }
@@ -1009,9 +879,9 @@ pg_status pg_max_bound(pg_composer *c, const pg_scalar *max_range, const pg_allo
         pg::MaxBoundGD<false>::Args A{};
         A.max_range = to_fr(max_range);
         A.n = (uint32_t)lay.num_bits;
-        A.witness = reinterpret_cast<const uint4 *>(c->d_stage);
-        A.witness_vars = c->d_stage + 4;
-        A.pow2 = c->e->d_pow2;
+        A.witness = reinterpret_cast<const uint4 *>(c->stage_words());
+        A.witness_vars = c->stage_words() + 4;
+        A.pow2 = c->e->d_pow2.as<uint4>();
         const pg_columns at = cols_at(c, c->n, c->nvars);
         PG_TRY(launch<pg::MaxBoundGD<false>>(c->e, A, &at, 1, c->n, c->nvars, c->zero_var, nullptr, nullptr, c->stream, nullptr, sa.in_place));
     }
@@ -1038,7 +908,7 @@ pg_status pg_scalar_decomposition_gadget(pg_composer *c, uint64_t num_bits, cons
     PG_TRY(stage(c, b, 5));
     const pg_columns at = cols_at(c, c->n, c->nvars);
     SignedAppend sa(c, gadget_sig(c, 43, pg::fr_zero(), pg::fr_zero(), num_bits, witness->var), lay.n_gates);
-    PG_TRY(decomposition_common(c->e, num_bits, c->d_stage + 4, reinterpret_cast<const pg_scalar *>(c->d_stage), 1, c->n, c->nvars, &at,
+    PG_TRY(decomposition_common(c->e, num_bits, c->stage_words() + 4, reinterpret_cast<const pg_scalar *>(c->stage_words()), 1, c->n, c->nvars, &at,
                                 nullptr, c->stream, sa.in_place));
     sa.commit();
     if (bits_out)
@@ -1223,8 +1093,8 @@ pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, con
     uint4 *va = c->val_ws.as<uint4>(), *vb = va + 2 * batch;
     const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_a_var, c->cols.vars, batch, va);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_b_var, c->cols.vars, batch, vb);
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_a_var, c->cols.view().vars, batch, va);
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_b_var, c->cols.view().vars, batch, vb);
     PG_HIP_TRY(hipGetLastError());
     const pg_columns at = cols_at(c, c->n, c->nvars);
     // (the rows: the two Variable arrays and where the call lands)
@@ -1255,26 +1125,10 @@ pg_status pg_composer_maybe_equal_batch(pg_composer *c, const pg_variable *d_a_v
 }
 
 namespace {
-// device arrays a ragged call keeps for the composer's lifetime
-struct RaggedBuffers {
-    uint64_t *row_off = nullptr, *var_off = nullptr;
-    uint32_t *num_bits = nullptr;
-    void release() {
-        if (row_off) (void)hipFree(row_off);
-        if (var_off) (void)hipFree(var_off);
-        if (num_bits) (void)hipFree(num_bits);
-    }
-    void keep(pg_composer *c) {
-        for (void *p : {(void *)row_off, (void *)var_off, (void *)num_bits})
-            if (p) c->ragged.push_back(p);
-    }
-};
 pg_status ragged_alloc(uint64_t batch, bool with_bits, RaggedBuffers *b) {
-    if (hipMalloc(&b->row_off, (batch + 1) * 8) != hipSuccess || hipMalloc(&b->var_off, (batch + 1) * 8) != hipSuccess ||
-        (with_bits && hipMalloc(&b->num_bits, batch * 4) != hipSuccess)) {
-        b->release();
+    if (b->row_off.reserve((batch + 1) * 8) != PG_OK || b->var_off.reserve((batch + 1) * 8) != PG_OK ||
+        (with_bits && b->num_bits.reserve(batch * 4) != PG_OK))
         return fail(PG_ERR_HIP, "hipMalloc of the call's prefix sums failed");
-    }
     return PG_OK;
 }
 }  // namespace
@@ -1306,21 +1160,20 @@ pg_status ragged_batch(pg_composer *c, uint32_t wire_kind, uint64_t batch, uint6
         st = emit(b, &at, sa.in_place);
         if (st == PG_OK) sa.commit();
     }
-    if (st != PG_OK) {
+    if (st != PG_OK) {  // (the buffers go once nothing reads them any more)
         (void)hipStreamSynchronize(c->stream);
-        b.release();
         return st;
     }
-    b.keep(c);
     // (per-item bounds: the largest item is the longest ladder there is)
     pg::PermSeg f = pg::footprint(c->n, c->nvars, batch, wire_kind, per_item_bounds ? 255u : 0u);
     if (per_item_bounds || errs) {
         f.gate_end = f.gate_base + lay.n_gates;
         f.var_end = f.var_base + lay.n_vars;
-        f.row_off = b.row_off;
-        f.var_off = b.var_off;
+        f.row_off = b.rows();
+        f.var_off = b.vars();
         f.wire_n = 0;
     }
+    c->ragged.push_back(std::move(b));
     add_footprint(c, f);
     c->n += lay.n_gates;
     c->nvars += lay.n_vars;
@@ -1343,7 +1196,7 @@ pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_
     return ragged_batch(
         c, pg::WIRES_MAX_BOUND, batch, nullptr,
         [&](RaggedBuffers &b, pg_layout *lay, uint64_t *) {
-            return pg_max_bound_ragged_plan(c->e, d_max_range, batch, b.num_bits, b.row_off, b.var_off, lay, c->stream);
+            return pg_max_bound_ragged_plan(c->e, d_max_range, batch, b.bits(), b.rows(), b.vars(), lay, c->stream);
         },
         [&](uint64_t, pg_composer::Sig *sig) {  // the rows: the per-item public bounds and where the call lands
             pg_composer::Sig dg;
@@ -1352,9 +1205,9 @@ pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
-            PG_TRY(max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.num_bits, b.row_off, b.var_off, c->n, c->nvars, at, d_result_vars,
+            PG_TRY(max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at, d_result_vars,
                                            c->stream, in_place));
-            if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits, batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+            if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits.get(), batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
                 return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
             return PG_OK;
         });
@@ -1374,20 +1227,20 @@ pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var
     uint4 *vals = c->val_ws.as<uint4>();
     const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_var, c->cols.vars, batch, vals);
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_var, c->cols.view().vars, batch, vals);
     PG_HIP_TRY(hipGetLastError());
     const pg_scalar *d_vals = reinterpret_cast<const pg_scalar *>(vals);
     return ragged_batch(
         c, pg::WIRES_IS_NON_ZERO, batch, err_count,
         [&](RaggedBuffers &b, pg_layout *lay, uint64_t *errs) {
-            return pg_is_non_zero_plan(c->e, d_vals, batch, b.row_off, b.var_off, d_err_mask, lay, errs, c->stream);
+            return pg_is_non_zero_plan(c->e, d_vals, batch, b.rows(), b.vars(), d_err_mask, lay, errs, c->stream);
         },
         [&](uint64_t errs, pg_composer::Sig *sig) {
             *sig = gadget_sig(c, 28, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs), dg);
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
-            return is_non_zero_common(c->e, d_var, d_vals, batch, b.row_off, b.var_off, c->n, c->nvars, c->zero_var, at, c->stream, in_place);
+            return is_non_zero_common(c->e, d_var, d_vals, batch, b.rows(), b.vars(), c->n, c->nvars, c->zero_var, at, c->stream, in_place);
         });
 }
 
@@ -1402,14 +1255,14 @@ pg_status pg_composer_scalar_mix_batch(pg_composer *c, const pg_scalar *d_v, con
     return ragged_batch(
         c, pg::WIRES_MIX, batch, err_count,
         [&](RaggedBuffers &b, pg_layout *lay, uint64_t *errs) {
-            return pg_scalar_mix_plan(c->e, d_v, batch, b.row_off, b.var_off, d_err_mask, lay, errs, c->stream);
+            return pg_scalar_mix_plan(c->e, d_v, batch, b.rows(), b.vars(), d_err_mask, lay, errs, c->stream);
         },
         [&](uint64_t errs, pg_composer::Sig *sig) {
             *sig = gadget_sig(c, 13, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs));
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
-            return scalar_mix_common(c->e, d_v, d_y, d_s, d_a, d_b, batch, b.row_off, b.var_off, c->n, c->nvars, c->zero_var, at, d_result_vars,
+            return scalar_mix_common(c->e, d_v, d_y, d_s, d_a, d_b, batch, b.rows(), b.vars(), c->n, c->nvars, c->zero_var, at, d_result_vars,
                                      c->stream, in_place);
         });
 }
@@ -1443,7 +1296,7 @@ pg_status gate_batch(pg_composer *c, uint32_t op, const pg_variable *d_a, const 
     B.a = d_a; B.b = d_b; B.c = creates ? nullptr : d_c; B.out_vars = d_out_vars;
     B.q_m = q_m; B.q_l = q_l; B.q_r = q_r; B.q_o = q_o; B.q_c = q_c;
     const uint64_t want = (batch + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 32;
-    hipLaunchKernelGGL(pg::gate_batch_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, B, c->cols);
+    hipLaunchKernelGGL(pg::gate_batch_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, B, c->cols.view());
     PG_HIP_TRY(hipGetLastError());
     sa.commit();
     // one row per item; add / mul: one Variable, a and b come from outside; the others: three Variables from outside, none created --
@@ -1489,7 +1342,7 @@ pg_status pg_composer_add_input_batch(pg_composer *c, const pg_scalar *d_scalars
     if (batch) {
         PG_TRY(check_scalars(d_scalars, "d_scalars"));
         PG_HIP_TRY(hipSetDevice(c->e->device));
-        PG_HIP_TRY(hipMemcpyAsync(c->cols.vars + 2 * c->nvars, d_scalars, batch * 32, hipMemcpyDeviceToDevice, c->stream));
+        PG_HIP_TRY(hipMemcpyAsync(c->cols.view().vars + 2 * c->nvars, d_scalars, batch * 32, hipMemcpyDeviceToDevice, c->stream));
     }
     *first_var = c->nvars;
     c->nvars += batch;
@@ -1520,26 +1373,23 @@ pg_status pg_composer_read_value(pg_composer *c, pg_variable v, pg_scalar *out) 
     if (!c || !out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     PG_TRY(flush(c));
     PG_TRY(check_var(c, v));
-    PG_HIP_TRY(hipMemcpyAsync(out, c->cols.vars + 2 * v, 32, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipMemcpyAsync(out, c->cols.view().vars + 2 * v, 32, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
     return PG_OK;
 }
 
-// upload the sparse public inputs / fourth-wire rows (small, rare): returns device buffers the caller frees
+// upload the sparse public inputs / fourth-wire rows (small, rare): into device buffers that live as long as B
 static pg_status upload_sparse(pg_composer *c, CallBuffers &B, uint64_t **d_gate, uint4 **d_val, pg::FourthWire **d_fw) {
     *d_gate = nullptr; *d_val = nullptr; *d_fw = nullptr;
     const size_t np = c->pi_gate.size(), nf = c->fourth.size();
     if (np) {
-        PG_HIP_TRY(hipMalloc(d_gate, np * 8));
-        B.own(*d_gate);
-        PG_HIP_TRY(hipMalloc(d_val, np * 32));
-        B.own(*d_val);
+        PG_TRY(B.take(d_gate, np * 8));
+        PG_TRY(B.take(d_val, np * 32));
         PG_HIP_TRY(hipMemcpyAsync(*d_gate, c->pi_gate.data(), np * 8, hipMemcpyHostToDevice, c->stream));
         PG_HIP_TRY(hipMemcpyAsync(*d_val, c->pi_val.data(), np * 32, hipMemcpyHostToDevice, c->stream));
     }
     if (nf) {
-        PG_HIP_TRY(hipMalloc(d_fw, nf * sizeof(pg::FourthWire)));
-        B.own(*d_fw);
+        PG_TRY(B.take(d_fw, nf * sizeof(pg::FourthWire)));
         PG_HIP_TRY(hipMemcpyAsync(*d_fw, c->fourth.data(), nf * sizeof(pg::FourthWire), hipMemcpyHostToDevice, c->stream));
     }
     return PG_OK;
@@ -1553,12 +1403,11 @@ pg_status pg_composer_check(pg_composer *c, int64_t *first_bad) {
     uint64_t *d_gate; uint4 *d_val; pg::FourthWire *d_fw;
     PG_TRY(upload_sparse(c, B, &d_gate, &d_val, &d_fw));
     unsigned long long *d_bad = nullptr, h_bad = ~0ull;
-    PG_HIP_TRY(hipMalloc(&d_bad, 8));
-    B.own(d_bad);
+    PG_TRY(B.take(&d_bad, 8));
     PG_HIP_TRY(hipMemcpyAsync(d_bad, &h_bad, 8, hipMemcpyHostToDevice, c->stream));
     const uint64_t want = (c->n + pg::kThreads - 1) / pg::kThreads;
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 8 ? (want ? want : 1) : (uint64_t)c->e->num_cus * 8);
-    hipLaunchKernelGGL(pg::check_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, c->cols, c->n, (uint64_t)0, c->nvars,
+    hipLaunchKernelGGL(pg::check_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, c->cols.view(), c->n, (uint64_t)0, c->nvars,
                        c->zero_var, d_gate, d_val, (uint32_t)c->pi_gate.size(), d_fw, (uint32_t)c->fourth.size(), d_bad);
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
@@ -1616,7 +1465,7 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
     const auto generic = [&](uint64_t lo, uint64_t hi) {
         if (hi <= lo) return;
         const uint64_t want = (2 * (hi - lo) + 16383) / 16384;
-        hipLaunchKernelGGL(pg::materialize_kernel, dim3((uint32_t)(want < grid ? want : grid)), dim3(pg::kThreads), 0, c->stream, c->cols, M,
+        hipLaunchKernelGGL(pg::materialize_kernel, dim3((uint32_t)(want < grid ? want : grid)), dim3(pg::kThreads), 0, c->stream, c->cols.view(), M,
                            lo, hi, c->zero_var);
     };
     uint64_t at = 0;
@@ -1644,7 +1493,7 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
         generic(at, s.gate_base);
         const uint64_t n_groups = (s.items + group - 1) / group, most = (uint64_t)c->e->num_cus * PG_MAT_GRID_PER_CU;
         const MatKernel kernel = r.mode != pg::MAT_SELF ? read_wires : r.ragged ? self_ragged[r.kind == pg::WIRES_MIX] : self[r.kind];
-        hipLaunchKernelGGL(kernel, dim3((uint32_t)(n_groups < most ? n_groups : most)), dim3(pg::kMatThreads), 0, c->stream, c->cols, M, s,
+        hipLaunchKernelGGL(kernel, dim3((uint32_t)(n_groups < most ? n_groups : most)), dim3(pg::kMatThreads), 0, c->stream, c->cols.view(), M, s,
                            (uint32_t)group, c->zero_var);
         at = s.gate_end;
     }
@@ -1654,7 +1503,7 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
     PG_TRY(upload_sparse(c, B, &d_gate, &d_val, &d_fw));
     if (d_fw)
         hipLaunchKernelGGL(pg::patch_fourth_kernel, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<uint4 *>(out->q_4), out->w_4,
-                           reinterpret_cast<uint4 *>(out->w_4_value), c->cols.vars, d_fw, (uint32_t)c->fourth.size());
+                           reinterpret_cast<uint4 *>(out->w_4_value), c->cols.view().vars, d_fw, (uint32_t)c->fourth.size());
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
     return PG_OK;
@@ -1696,7 +1545,6 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
     PG_HIP_TRY(hipSetDevice(c->e->device));
     PG_TRY(perm_kernel_attributes(c->e));
     const uint32_t grid = (uint32_t)c->e->num_cus * 32;
-    if (!c->h_total) PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&c->h_total), 32, hipHostMallocDefault));
     uint32_t pos_bits = 2, var_bits = 1;
     while ((1ull << pos_bits) < 4 * c->n) pos_bits++;
     while ((1ull << var_bits) < c->nvars + 1) var_bits++;  // (one number more than there are Variables: the holes' key)
@@ -1722,7 +1570,7 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
     PG_TRY(perm_reserve(c, c->perm_small, seg_bytes + fw_bytes + 256));
     char *small = c->perm_small.as<char>();
     pg::PermCtx X;
-    X.C = c->cols; X.n = c->n; X.padded_n = padded_n; X.zero_var = c->zero_var;
+    X.C = c->cols.view(); X.n = c->n; X.padded_n = padded_n; X.zero_var = c->zero_var;
     X.segs = reinterpret_cast<const pg::PermSeg *>(small); X.n_segs = (uint32_t)segs.size();
     X.fw = reinterpret_cast<const pg::FourthWire *>(small + seg_bytes); X.n_fw = (uint32_t)c->fourth.size();
     X.fw_lo = 0; X.fw_span = 0; X.pos_bits = pos_bits;
@@ -1817,10 +1665,10 @@ pg_status pg_composer_permutation(pg_composer *c, uint64_t padded_n, uint64_t *d
             hipLaunchKernelGGL(pg::perm_gap_kernel, dim3((uint32_t)nblk), dim3(pg::kThreads), 0, c->stream, X, g.first, g.second, Q,
                                d_sigma);
         }
-        PG_HIP_TRY(hipMemcpyAsync(c->h_total, d_count, 16, hipMemcpyDeviceToHost, c->stream));
+        PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_count, 16, hipMemcpyDeviceToHost, c->stream));
         PG_HIP_TRY(hipStreamSynchronize(c->stream));
-        nS = c->h_total[0];
-        holes = c->h_total[1];
+        nS = c->totals()[0];
+        holes = c->totals()[1];
         c->perm_last_sparse = nS;
         if (nS <= cap) break;
         if (attempt) return fail(PG_ERR_HIP, "sparse position list grew between two passes");
@@ -1867,14 +1715,14 @@ pg_status pg_check_rows(pg_engine *e, const pg_columns *cols, uint64_t n_gates, 
     C.w[0] = cols->w_l; C.w[1] = cols->w_r; C.w[2] = cols->w_o;
     C.vars = reinterpret_cast<uint4 *>(cols->var_values);
     unsigned long long *d_bad = nullptr, h_bad = ~0ull;
-    PG_HIP_TRY(hipMalloc(&d_bad, 8));
+    CallBuffers B(st);
+    PG_TRY(B.take(&d_bad, 8));
     PG_HIP_TRY(hipMemcpyAsync(d_bad, &h_bad, 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(pg::check_kernel, dim3((uint32_t)e->num_cus * 16), dim3(pg::kThreads), 0, st, C, n_gates, var_base, n_vars,
                        zero_var, (const uint64_t *)nullptr, (const uint4 *)nullptr, 0u, (const pg::FourthWire *)nullptr, 0u, d_bad);
     hipError_t le = hipGetLastError();
     if (le == hipSuccess) le = hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, st);
     if (le == hipSuccess) le = hipStreamSynchronize(st);
-    (void)hipFree(d_bad);
     if (le != hipSuccess) return fail(PG_ERR_HIP, std::string("pg_check_rows: ") + hipGetErrorString(le));
     *first_bad = h_bad == ~0ull ? -1 : (int64_t)h_bad;
     return PG_OK;

@@ -25,7 +25,7 @@ struct pg_comm {
     ncclComm_t comm = nullptr;
     int rank = 0, world = 1;
     bool owned = false;  // created by pg_comm_create (destroyed with it) or adopted from the host
-    uint64_t *d_totals = nullptr;  // 2 + 2 * world words: the staging buffer of the ragged plans' totals exchange
+    Scratch d_totals;  // 2 + 2 * world words: the staging buffer of the ragged plans' totals exchange
 };
 
 namespace {
@@ -98,6 +98,25 @@ pg_status rccl() {
         ncclResult_t _r = (expr);                                                                           \
         if (_r != ncclSuccess) return fail(PG_ERR_HIP, std::string(#expr) + ": " + g_rccl.GetErrorString(_r)); \
     } while (0)
+
+// the handle of a communicator of `world` ranks, with its staging words on the engine's device; an owned communicator is
+// destroyed with the handle, also when this fails
+pg_status comm_handle(pg_engine *e, ncclComm_t comm, int rank, int world, bool owned, pg_comm **out) {
+    std::unique_ptr<pg_comm, void (*)(pg_comm *)> c(new (std::nothrow) pg_comm(), pg_comm_destroy);
+    if (!c) {
+        if (owned) (void)g_rccl.CommDestroy(comm);
+        return fail(PG_ERR_HIP, "out of host memory");
+    }
+    c->e = e;
+    c->comm = comm;
+    c->rank = rank;
+    c->world = world;
+    c->owned = owned;
+    if (hipSetDevice(e->device) != hipSuccess || c->d_totals.reserve((2 + 2 * (size_t)world) * sizeof(uint64_t)) != PG_OK)
+        return fail(PG_ERR_HIP, "hipMalloc(totals staging)");
+    *out = c.release();
+    return PG_OK;
+}
 
 inline uint64_t up2(uint64_t words) { return (words + 15) & ~15ull; }  // sections of a packed chunk start on 128-byte lines (the sweeps' wave stores do)
 
@@ -204,22 +223,7 @@ pg_status pg_comm_create(pg_engine *e, const uint8_t id[PG_COMM_ID_BYTES], uint3
     std::memcpy(u.internal, id, PG_COMM_ID_BYTES);
     ncclComm_t comm = nullptr;
     PG_NCCL_TRY(g_rccl.CommInitRank(&comm, (int)world, u, (int)rank));
-    pg_comm *c = new (std::nothrow) pg_comm();
-    if (!c) {
-        (void)g_rccl.CommDestroy(comm);
-        return fail(PG_ERR_HIP, "out of host memory");
-    }
-    c->e = e;
-    c->comm = comm;
-    c->rank = (int)rank;
-    c->world = (int)world;
-    c->owned = true;
-    if (hipMalloc(reinterpret_cast<void **>(&c->d_totals), (2 + 2 * (size_t)world) * sizeof(uint64_t)) != hipSuccess) {
-        pg_comm_destroy(c);
-        return fail(PG_ERR_HIP, "hipMalloc(totals staging)");
-    }
-    *out = c;
-    return PG_OK;
+    return comm_handle(e, comm, (int)rank, (int)world, true, out);
 }
 
 pg_status pg_comm_adopt(pg_engine *e, void *nccl_comm, pg_comm **out) {
@@ -229,27 +233,14 @@ pg_status pg_comm_adopt(pg_engine *e, void *nccl_comm, pg_comm **out) {
     int n = 0, r = 0;
     PG_NCCL_TRY(g_rccl.CommCount(static_cast<ncclComm_t>(nccl_comm), &n));
     PG_NCCL_TRY(g_rccl.CommUserRank(static_cast<ncclComm_t>(nccl_comm), &r));
-    pg_comm *c = new (std::nothrow) pg_comm();
-    if (!c) return fail(PG_ERR_HIP, "out of host memory");
-    c->e = e;
-    c->comm = static_cast<ncclComm_t>(nccl_comm);
-    c->rank = r;
-    c->world = n;
-    c->owned = false;
-    if (hipSetDevice(e->device) != hipSuccess ||
-        hipMalloc(reinterpret_cast<void **>(&c->d_totals), (2 + 2 * (size_t)n) * sizeof(uint64_t)) != hipSuccess) {
-        pg_comm_destroy(c);
-        return fail(PG_ERR_HIP, "hipMalloc(totals staging)");
-    }
-    *out = c;
-    return PG_OK;
+    return comm_handle(e, static_cast<ncclComm_t>(nccl_comm), r, n, false, out);
 }
 
+// ordering only: the engine's device current, an owned communicator destroyed before its staging words go
 void pg_comm_destroy(pg_comm *c) {
     if (!c) return;
     (void)hipSetDevice(c->e->device);
     if (c->owned && c->comm && g_rccl.ok) (void)g_rccl.CommDestroy(c->comm);
-    if (c->d_totals) (void)hipFree(c->d_totals);
     delete c;
 }
 
@@ -305,29 +296,23 @@ struct pg_gather_pipeline {
     bool vars_only = false;
     pg_layout lay{};
     pg_packed packed{};   // a rank's chunk: all nine arrays (packed mode) / the eight row arrays (variables-only mode)
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t ready[2] = {nullptr, nullptr}, done[2] = {nullptr, nullptr};
+    Stream comm_stream;
+    Event ready[2], done[2];
     // packed mode: local[b] = this rank's chunk, gathered[b] = every rank's; variables-only: gathered[b] = every rank's rows
     // (regenerated here), own[b] = this rank's variable table, vars[b] = every rank's
-    uint64_t *local[2] = {nullptr, nullptr}, *gathered[2] = {nullptr, nullptr}, *own[2] = {nullptr, nullptr}, *vars[2] = {nullptr, nullptr};
-    pg_variable *res = nullptr;
+    Scratch local[2], gathered[2], own[2], vars[2];  // (words: uint64_t)
+    Scratch res;                                     // pg_variable per item of a chunk
     std::vector<pg_columns> parts[2];
     pg_columns mine[2];   // where this rank's emission of a slot goes
 };
 
 extern "C" {
 
+// ordering only: the pipeline's device current, its communication stream drained.  The members release themselves.
 void pg_range_check_gather_pipeline_destroy(pg_gather_pipeline *p) {
     if (!p) return;
     (void)hipSetDevice(p->device);
-    if (p->comm_stream) { (void)hipStreamSynchronize(p->comm_stream); (void)hipStreamDestroy(p->comm_stream); }
-    for (int b = 0; b < 2; b++) {
-        if (p->ready[b]) (void)hipEventDestroy(p->ready[b]);
-        if (p->done[b]) (void)hipEventDestroy(p->done[b]);
-        for (uint64_t *q : {p->local[b], p->gathered[b], p->own[b], p->vars[b]})
-            if (q) (void)hipFree(q);
-    }
-    if (p->res) (void)hipFree(p->res);
+    (void)hipStreamSynchronize(p->comm_stream.get());
     delete p;
 }
 
@@ -339,7 +324,8 @@ pg_status pg_range_check_gather_pipeline_create(pg_comm *c, const pg_scalar *min
     pg_layout lay;
     PG_TRY(pg_range_check_layout(min_range, max_range, chunk, &lay));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    pg_gather_pipeline *p = new (std::nothrow) pg_gather_pipeline();
+    // (nothing is enqueued here: on a failure the members release themselves, the device current)
+    std::unique_ptr<pg_gather_pipeline> p(new (std::nothrow) pg_gather_pipeline());
     if (!p) return fail(PG_ERR_HIP, "out of host memory");
     p->c = c;
     p->device = c->e->device;
@@ -350,40 +336,35 @@ pg_status pg_range_check_gather_pipeline_create(pg_comm *c, const pg_scalar *min
     p->lay = lay;
     const uint64_t world = (uint64_t)c->world, G = lay.n_gates, V = lay.n_vars;
     pg_status st = pg_packed_layout(G, p->vars_only ? 0 : V, &p->packed);
-    auto bail = [&](pg_status s, const char *what) {
-        pg_range_check_gather_pipeline_destroy(p);
-        return s == PG_OK ? PG_OK : fail(s, what);
-    };
-    if (st != PG_OK) return bail(st, "packed layout");
+    if (st != PG_OK) return fail(st, "packed layout");
     const uint64_t words = p->packed.total_words;
-    if (hipStreamCreateWithFlags(&p->comm_stream, hipStreamNonBlocking) != hipSuccess) return bail(PG_ERR_HIP, "communication stream");
-    if (hipMalloc(reinterpret_cast<void **>(&p->res), chunk * sizeof(pg_variable)) != hipSuccess) return bail(PG_ERR_HIP, "hipMalloc");
+    if (p->comm_stream.create(hipStreamNonBlocking) != PG_OK) return fail(PG_ERR_HIP, "communication stream");
+    if (p->res.reserve(chunk * sizeof(pg_variable)) != PG_OK) return fail(PG_ERR_HIP, "hipMalloc");
     for (int b = 0; b < 2; b++) {
-        if (hipEventCreateWithFlags(&p->ready[b], hipEventDisableTiming) != hipSuccess ||
-            hipEventCreateWithFlags(&p->done[b], hipEventDisableTiming) != hipSuccess)
-            return bail(PG_ERR_HIP, "events");
-        if (hipMalloc(reinterpret_cast<void **>(&p->gathered[b]), world * words * 8) != hipSuccess) return bail(PG_ERR_HIP, "hipMalloc(gathered chunk)");
+        if (p->ready[b].create(hipEventDisableTiming) != PG_OK || p->done[b].create(hipEventDisableTiming) != PG_OK)
+            return fail(PG_ERR_HIP, "events");
+        if (p->gathered[b].reserve(world * words * 8) != PG_OK) return fail(PG_ERR_HIP, "hipMalloc(gathered chunk)");
         if (p->vars_only) {
-            if (hipMalloc(reinterpret_cast<void **>(&p->own[b]), V * 32) != hipSuccess ||
-                hipMalloc(reinterpret_cast<void **>(&p->vars[b]), world * V * 32) != hipSuccess)
-                return bail(PG_ERR_HIP, "hipMalloc(variable tables)");
-        } else if (hipMalloc(reinterpret_cast<void **>(&p->local[b]), words * 8) != hipSuccess) {
-            return bail(PG_ERR_HIP, "hipMalloc(local chunk)");
+            if (p->own[b].reserve(V * 32) != PG_OK || p->vars[b].reserve(world * V * 32) != PG_OK)
+                return fail(PG_ERR_HIP, "hipMalloc(variable tables)");
+        } else if (p->local[b].reserve(words * 8) != PG_OK) {
+            return fail(PG_ERR_HIP, "hipMalloc(local chunk)");
         }
         p->parts[b].resize(world);
         for (uint64_t r = 0; r < world; r++) {
             pg_columns &pc = p->parts[b][r];
-            if ((st = pg_columns_in_packed(p->gathered[b] + r * words, G, p->vars_only ? 0 : V, &pc)) != PG_OK) return bail(st, "packed view");
-            if (p->vars_only) pc.var_values = reinterpret_cast<pg_scalar *>(p->vars[b] + r * V * 4);
+            if ((st = pg_columns_in_packed(p->gathered[b].as<uint64_t>() + r * words, G, p->vars_only ? 0 : V, &pc)) != PG_OK)
+                return fail(st, "packed view");
+            if (p->vars_only) pc.var_values = reinterpret_cast<pg_scalar *>(p->vars[b].as<uint64_t>() + r * V * 4);
         }
         if (p->vars_only) {  // own rows straight into their place among everybody's, own variables into the send buffer
             p->mine[b] = p->parts[b][(uint64_t)c->rank];
-            p->mine[b].var_values = reinterpret_cast<pg_scalar *>(p->own[b]);
-        } else if ((st = pg_columns_in_packed(p->local[b], G, V, &p->mine[b])) != PG_OK) {
-            return bail(st, "packed view");
+            p->mine[b].var_values = p->own[b].as<pg_scalar>();
+        } else if ((st = pg_columns_in_packed(p->local[b].get(), G, V, &p->mine[b])) != PG_OK) {
+            return fail(st, "packed view");
         }
     }
-    *out = p;
+    *out = p.release();
     return PG_OK;
 }
 
@@ -407,7 +388,7 @@ pg_status pg_range_check_gather_pipeline_run(pg_gather_pipeline *p, const pg_sca
     uint64_t pending_chunk = 0;
     auto finish = [&]() -> pg_status {  // the chunk on the links is complete for `st`; hand it over
         if (pending_slot < 0) return PG_OK;
-        PG_HIP_TRY(hipStreamWaitEvent(st, p->done[pending_slot], 0));
+        PG_HIP_TRY(hipStreamWaitEvent(st, p->done[pending_slot].get(), 0));
         if (consume) consume(user, pending_chunk, (uint32_t)world, p->parts[pending_slot].data(), p->lay.n_gates, p->lay.n_vars, stream);
         pending_slot = -1;
         return PG_OK;
@@ -420,7 +401,7 @@ pg_status pg_range_check_gather_pipeline_run(pg_gather_pipeline *p, const pg_sca
             const uint64_t who = p->vars_only ? r : rank, first = who * total_per_rank + k * p->chunk;
             if (who == rank) {
                 PG_TRY(pg_range_check_batch(e, &p->mn, &p->mx, d_witness_local + k * p->chunk, p->chunk, gate_base + first * G,
-                                            var_base + first * V, &p->mine[b], p->res, stream));
+                                            var_base + first * V, &p->mine[b], p->res.as<pg_variable>(), stream));
             } else {
                 PG_TRY(pg_range_check_structure_batch(e, &p->mn, &p->mx, p->chunk, gate_base + first * G, var_base + first * V,
                                                       &p->parts[b][r], stream));
@@ -429,11 +410,11 @@ pg_status pg_range_check_gather_pipeline_run(pg_gather_pipeline *p, const pg_sca
         PG_TRY(finish());  // chunk k - 1 (it travelled while chunk k was being emitted)
         // the collective of chunk k on the communication stream, behind the emission and behind everything the consumers
         // of earlier chunks have enqueued (they may still be reading the slot's gathered buffer)
-        PG_HIP_TRY(hipEventRecord(p->ready[b], st));
-        PG_HIP_TRY(hipStreamWaitEvent(p->comm_stream, p->ready[b], 0));
-        if (p->vars_only) PG_TRY(pg_allgather_bytes(c, p->own[b], p->vars[b], p->lay.n_vars * 32, p->comm_stream));
-        else PG_TRY(pg_allgather_bytes(c, p->local[b], p->gathered[b], p->packed.total_words * 8, p->comm_stream));
-        PG_HIP_TRY(hipEventRecord(p->done[b], p->comm_stream));
+        PG_HIP_TRY(hipEventRecord(p->ready[b].get(), st));
+        PG_HIP_TRY(hipStreamWaitEvent(p->comm_stream.get(), p->ready[b].get(), 0));
+        if (p->vars_only) PG_TRY(pg_allgather_bytes(c, p->own[b].get(), p->vars[b].get(), p->lay.n_vars * 32, p->comm_stream.get()));
+        else PG_TRY(pg_allgather_bytes(c, p->local[b].get(), p->gathered[b].get(), p->packed.total_words * 8, p->comm_stream.get()));
+        PG_HIP_TRY(hipEventRecord(p->done[b].get(), p->comm_stream.get()));
         pending_slot = b;
         pending_chunk = k;
     }
@@ -459,7 +440,7 @@ pg_status pg_max_bound_ragged_sharded_plan(pg_comm *c, const pg_scalar *d_max_ra
         all[1] = lay.n_vars;
     } else {  // 16 bytes per rank through the collective, staged in the communicator's device words
         PG_HIP_TRY(hipSetDevice(e->device));
-        uint64_t *d = c->d_totals;
+        uint64_t *d = c->d_totals.as<uint64_t>();
         const uint64_t mine[2] = {planned == PG_OK ? lay.n_gates : kFailed, planned == PG_OK ? lay.n_vars : kFailed};
         hipStream_t st = static_cast<hipStream_t>(stream);
         // (from here on nothing returns before the collective has been enqueued)

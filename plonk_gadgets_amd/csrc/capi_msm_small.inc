@@ -9,23 +9,10 @@ namespace {
 // the segment offsets travel through a pinned buffer of the engine, so the copy is asynchronous and the caller's array is
 // free when the call returns; the buffer is rewritten only once the copy of the call before has left it
 pg_status stage_offsets(pg_engine *e, const uint64_t *seg_off, uint64_t count, uint64_t *d_off, hipStream_t st) {
-    if (!e->ev_seg) PG_HIP_TRY(hipEventCreateWithFlags(&e->ev_seg, hipEventDisableTiming));
-    if (e->seg_pending) {
-        PG_HIP_TRY(hipEventSynchronize(e->ev_seg));
-        e->seg_pending = false;
-    }
-    if (count > e->seg_cap) {
-        if (e->h_seg) (void)hipHostFree(e->h_seg);
-        e->h_seg = nullptr;
-        e->seg_cap = 0;
-        const uint64_t cap = count < 1024 ? 1024 : count;
-        PG_HIP_TRY(hipHostMalloc(reinterpret_cast<void **>(&e->h_seg), cap * sizeof(uint64_t), hipHostMallocDefault));
-        e->seg_cap = cap;
-    }
-    std::memcpy(e->h_seg, seg_off, count * sizeof(uint64_t));
-    PG_HIP_TRY(hipMemcpyAsync(d_off, e->h_seg, count * sizeof(uint64_t), hipMemcpyHostToDevice, st));
-    PG_HIP_TRY(hipEventRecord(e->ev_seg, st));
-    e->seg_pending = true;
+    PG_TRY(e->seg.acquire((count < 1024 ? 1024 : count) * sizeof(uint64_t), false));
+    std::memcpy(e->seg.host(), seg_off, count * sizeof(uint64_t));
+    PG_HIP_TRY(hipMemcpyAsync(d_off, e->seg.host(), count * sizeof(uint64_t), hipMemcpyHostToDevice, st));
+    PG_HIP_TRY(e->seg.sent(st));
     return PG_OK;
 }
 

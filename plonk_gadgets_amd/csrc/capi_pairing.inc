@@ -5,7 +5,7 @@
 
 struct pg_g2_prepared {
     int device = -1;
-    pg::G2Line *d_lines = nullptr;  // kAteLines lines on the device
+    Scratch lines;  // kAteLines lines (pg::G2Line) on the device
 };
 
 namespace {
@@ -32,9 +32,9 @@ pg_status launch_pairing(pg_engine *e, const pg_g1_affine *d_points, const pg_g2
     PG_TRY(check_scalars(d_points, "d_points"));
     pg::PairingLines L{};
     for (uint64_t j = 0; j < n_pairs; j++) {
-        if (!prepared[j] || !prepared[j]->d_lines) return fail(PG_ERR_INVALID_ARGUMENT, "a prepared point is NULL");
+        if (!prepared[j] || !prepared[j]->lines.get()) return fail(PG_ERR_INVALID_ARGUMENT, "a prepared point is NULL");
         if (prepared[j]->device != e->device) return fail(PG_ERR_INVALID_ARGUMENT, "a prepared point lives on another device");
-        L.q[j] = prepared[j]->d_lines;
+        L.q[j] = prepared[j]->lines.as<pg::G2Line>();
     }
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
@@ -104,23 +104,20 @@ pg_status pg_g2_prepare(pg_engine *e, const pg_g2_affine *q, pg_g2_prepared **ou
     std::vector<pg::G2Line> lines(pg::kAteLines);
     pg::g2_prepare(a, lines.data());
     PG_HIP_TRY(hipSetDevice(e->device));
-    pg_g2_prepared *p = new (std::nothrow) pg_g2_prepared;
+    std::unique_ptr<pg_g2_prepared> p(new (std::nothrow) pg_g2_prepared);
     if (!p) return fail(PG_ERR_HIP, "out of host memory");
     p->device = e->device;
-    hipError_t err = hipMalloc(reinterpret_cast<void **>(&p->d_lines), lines.size() * sizeof(pg::G2Line));
-    if (err == hipSuccess) err = hipMemcpy(p->d_lines, lines.data(), lines.size() * sizeof(pg::G2Line), hipMemcpyHostToDevice);
-    if (err != hipSuccess) {
-        if (p->d_lines) (void)hipFree(p->d_lines);
-        delete p;
-        return fail(PG_ERR_HIP, std::string("pg_g2_prepare: ") + hipGetErrorString(err));
-    }
-    *out = p;
+    const uint64_t bytes = lines.size() * sizeof(pg::G2Line);
+    if (p->lines.reserve(bytes) != PG_OK) return fail(PG_ERR_HIP, std::string("pg_g2_prepare: ") + pg_last_error());
+    const hipError_t err = hipMemcpy(p->lines.get(), lines.data(), bytes, hipMemcpyHostToDevice);
+    if (err != hipSuccess) return fail(PG_ERR_HIP, std::string("pg_g2_prepare: ") + hipGetErrorString(err));
+    *out = p.release();
     return PG_OK;
 }
 
 void pg_g2_prepared_destroy(pg_g2_prepared *p) {
     if (!p) return;
-    if (p->d_lines) (void)hipFree(p->d_lines);
+    (void)hipSetDevice(p->device);
     delete p;
 }
 

@@ -5,15 +5,10 @@
 // that appends one row and/or one variable, the gadgets append through the batched emitters (emit.hpp).
 #pragma once
 
+#include "composer_cols.hpp"
 #include "emit.hpp"
 
 namespace pg {
-
-struct ComposerCols {
-    uint4 *q[5];
-    uint64_t *w[3];
-    uint4 *vars;
-};
 
 enum GateOp : uint32_t { OP_ADD_INPUT = 0, OP_ROW = 1, OP_ADD = 2, OP_MUL = 3 };
 // OR-ed into GateCmd::op: the row is already in the columns (a witness refresh, pg_composer_clear_witness) -- only the

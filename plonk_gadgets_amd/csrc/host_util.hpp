@@ -1,6 +1,6 @@
 // host_util.hpp -- what the host side of the C ABI (capi.hip and its capi_*.inc) shares: workspace layouts (Carve), the
-// engine's grow-only device buffers (Scratch), status plumbing and argument checks.  Included by capi.hip alone, before
-// anything that uses it.  The first part needs no HIP: a plain host compiler sees it alone (tests/cpp/carve_host.cpp, g++).
+// owners of everything allocated or created (owners.hpp), status plumbing and argument checks.  Included by capi.hip alone,
+// before anything that uses it.  The first part needs no HIP: a plain host compiler sees it alone (tests/cpp/carve_host.cpp, g++).
 #pragma once
 
 #include <cstdint>
@@ -39,68 +39,11 @@ class Carve {
 
 #include "../../include/plonk_gadgets_hip.h"
 #include "fr.hpp"
+#include "owners.hpp"  // fail, PG_TRY, PG_HIP_TRY; Scratch, Pinned, Event, Stream, Staging, CallBuffers, ColumnStore
 
 namespace {
 
-using pg::Carve;
 using pg::round256;
-
-thread_local std::string g_last_error;
-
-pg_status fail(pg_status s, const std::string &msg) {
-    g_last_error = msg;
-    return s;
-}
-
-#define PG_HIP_TRY(expr)                                                                \
-    do {                                                                                \
-        hipError_t _e = (expr);                                                         \
-        if (_e != hipSuccess)                                                           \
-            return fail(PG_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e)); \
-    } while (0)
-
-#define PG_TRY(expr)                   \
-    do {                               \
-        pg_status _s = (expr);         \
-        if (_s != PG_OK) return _s;    \
-    } while (0)
-
-// A grow-only device buffer that owns its memory.  reserve() allocates on the CURRENT device and neither synchronises nor
-// clears: a caller whose buffer may still be read by work in flight orders that itself (hipFree waits for the device).
-class Scratch {
-  public:
-    Scratch() = default;
-    Scratch(const Scratch &) = delete;
-    Scratch &operator=(const Scratch &) = delete;
-    ~Scratch() {
-        if (p_) (void)hipFree(p_);
-    }
-    // at least `bytes`; what the buffer held is lost when it grows, and a failed allocation leaves it empty
-    pg_status reserve(uint64_t bytes) {
-        if (bytes <= bytes_) return PG_OK;
-        if (p_) (void)hipFree(p_);
-        p_ = nullptr;
-        bytes_ = 0;
-        PG_HIP_TRY(hipMalloc(&p_, bytes));
-        bytes_ = bytes;
-        return PG_OK;
-    }
-    // reserve what `layout` measures, then let it place its parts: layout(Carve) names the parts and returns Carve::bytes()
-    template <class Layout>
-    pg_status carve(uint64_t align, Layout &&layout) {
-        PG_TRY(reserve(layout(Carve(align))));
-        layout(Carve(align, p_));
-        return PG_OK;
-    }
-    void *get() const { return p_; }
-    uint64_t size() const { return bytes_; }
-    template <typename T>
-    T *as() const { return static_cast<T *>(p_); }
-
-  private:
-    void *p_ = nullptr;
-    uint64_t bytes_ = 0;
-};
 
 inline pg::Fr to_fr(const pg_scalar *s) {
     pg::Fr f;

@@ -917,6 +917,81 @@ def test_spread_columns_keeps_the_circuit(engine):
     assert np.array_equal(dev.permutation(padded).cpu().numpy().view(np.uint64), ora.sigma(padded))
 
 
+def more_rows_than_the_card_holds() -> int:
+    """a capacity whose FIRST array -- one selector column, 32 bytes a row -- is twice the card's memory: the allocator refuses it
+    at once, before anything is written"""
+    return torch.cuda.get_device_properties(0).total_memory // 16
+
+
+@pytest.mark.parametrize("spread,message", [(False, "capacity"), (True, "must exist beside the old one")], ids=["separate", "spread"])
+def test_failed_growth_leaves_the_composer_intact(engine, spread, message):
+    """a reserve() the device cannot satisfy fails with the call's own message -- nine separate arrays: the first allocation is
+    refused; one block: it is said before the allocation is tried -- and the composer is what it was: capacity, every column, the
+    check.  No error stays behind: a range_check right afterwards (it grows the composer) appends and checks"""
+    dev = pg.StandardComposer(engine, gate_capacity=8, var_capacity=8)
+    dev.constrain_to_constant(dev.add_input(S(5)), S(5), None)
+    if spread:
+        dev.spread_columns(1 / 1024)
+    before, cap = dev.export(), dev.capacity()
+    assert cap == (8, 8) and dev.check() == -1
+    with pytest.raises(pg.PgError, match=message):
+        dev.reserve(more_rows_than_the_card_holds(), 8)
+    assert dev.capacity() == cap
+    after = dev.export()
+    for k in COLS:
+        assert np.array_equal(before[k], after[k]), k
+    assert dev.check() == -1
+    dev.auto_grow()
+    r = pg.range_check(dev, S(0), S(2**64), pg.AllocatedScalar.allocate(dev, S(1)))
+    assert dev.value(r).to_int() == 1 and dev.check() == -1
+    after = dev.export()
+    for k in COLS:
+        assert np.array_equal(before[k], after[k][:len(before[k])]), k
+
+
+def test_a_create_that_cannot_be_satisfied(engine):
+    """a composer the device has no room for is an error, and the engine makes a normal one afterwards"""
+    from oracle import pyoracle as po
+    with pytest.raises(pg.PgError, match="hipMalloc of the composer columns failed"):
+        pg.StandardComposer(engine, gate_capacity=more_rows_than_the_card_holds(), var_capacity=8)
+    dev = pg.StandardComposer(engine, gate_capacity=8, var_capacity=8)
+    same(dev, po.Composer())
+    assert dev.check() == -1
+
+
+def test_ragged_calls_keep_their_prefix_sums_until_the_witness_is_cleared(engine):
+    """the device arrays of ragged calls (an is_non_zero batch with a failing item keeps its prefix sums, a max_bound batch with
+    per-item bounds its ladder lengths too) serve sigma, go at clear_witness, come again with the next build and go with the
+    composer: sigma == the oracle's both times, and a new composer on the same engine is sound afterwards"""
+    import ctypes as C
+    from oracle import pyoracle as po
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.int64)).to("cuda:0")
+    dev = pg.StandardComposer(engine, gate_capacity=8, var_capacity=8)
+    dev.auto_grow()
+    nb = C.c_uint64()
+    for build, (values, witnesses) in enumerate((([3, 0, 9], [100, 70000, 5]), ([8, 0, 2], [1, 2**40, 2**62]))):
+        if build:
+            dev.clear_witness()
+        ora = po.Composer()
+        vals = synth.scalars_from_ints(values)
+        first = dev.add_input_batch(t(vals))
+        ovars = [ora.add_input(v) for v in vals]
+        assert first == ovars[0]
+        err, nerr = dev.is_non_zero_batch(torch.arange(first, first + 3, dtype=torch.int64, device="cuda:0"))
+        assert err.cpu().numpy().tolist() == [int(ora.L.is_non_zero(ora.c, ovars[i], po.fr(vals[i]))) for i in range(3)] and nerr == 1
+        bounds, wit = synth.scalars_from_ints([2**7 + 1, 2**20, 2**63 + 5]), synth.scalars_from_ints(witnesses)
+        res, _ = dev.max_bound_ragged_batch(t(bounds), t(wit))
+        ores = [int(ora.L.max_bound(ora.c, po.fr(b), ora.allocate(w), C.byref(nb))) for b, w in zip(bounds, wit)]
+        assert list(res.cpu().numpy().view(np.uint64)) == ores
+        same(dev, ora)
+        padded = 1 << (dev.circuit_size() - 1).bit_length()
+        assert np.array_equal(dev.permutation(padded).cpu().numpy().view(np.uint64), ora.sigma(padded))
+    dev.close()  # (with the second build's arrays alive)
+    dev = pg.StandardComposer(engine, gate_capacity=8, var_capacity=8)
+    same(dev, po.Composer())
+    assert dev.circuit_size() == 3 and dev.check() == -1
+
+
 def test_two_host_threads_two_composers():
     """one engine + composer per host thread (ctypes releases the GIL during the calls): both threads build the golden
     circuit twenty times over, each result equals the fixture"""
