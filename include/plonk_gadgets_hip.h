@@ -573,6 +573,19 @@ enum { PG_QUOTIENT_SCRATCH_COLS = 8 };
 pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
                       const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
                       pg_scalar *d_t, pg_scalar *d_scratch, void *stream);
+/* pg_quotient_blinded: the same quotient for blinded wire and permutation polynomials (the PLONK paper's rounds 1 and 2; DESIGN
+ * section 3.17), which is what makes a proof zero-knowledge.  p->w[j] points at n + 2 coefficients, w_j = w_j0 + (b1 X + b0)(X^n - 1),
+ * and p->z at n + 3, z = z0 + (b2 X^2 + b1 X + b0)(X^n - 1): plain coefficient arrays, rows n.. the blinders and the low rows less
+ * them.  Every other input has n coefficients, as above.  N then has degree <= 5n + 6, and d_t gets 4n + 8 scalars: t_lo | t_mid |
+ * t_hi | t_4th with t_4th of n + 8 rows, the last of them 0.  With T_i the coefficient 5n + i of N (i < 7) and t~ the polynomial of
+ * degree < 4n with t~(x) = N(x) / (x^n - 1) on the 4n points, d_t[4n + i] = T_i, d_t[k] = t~[k] - coset_gen^(4n) T_k for k < 7 and
+ * d_t[k] = t~[k] for the other k < 4n: for a satisfied circuit, exactly N / (X^n - 1).  The transforms stay n-point ones: one more
+ * pointwise step per chunk adds x^n times the blinders' terms to the wires' and z's values, and one lane computes the T_i from the
+ * top seven coefficients of the permutation products' factors.  With blinders of zero, rows 0..4n-1 are pg_quotient's.
+ * 3 <= log2_n <= 30; d_scratch and every check as for pg_quotient, overlaps against the longer extents; the call only enqueues. */
+pg_status pg_quotient_blinded(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha,
+                              const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4],
+                              const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream);
 /* pg_poly_evaluate: d_out[j] = sum_{i < n} c_j[i] point^i for the n_cols columns c_j = d_coeffs + j * col_stride (device,
  * Montgomery form; 1 <= n <= 2^32, col_stride >= n; point^0 = 1, so point = 0 gives c_j[0]).  A bad n or stride, a NULL or
  * misaligned pointer, or a point not reduced below the modulus -> PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise

@@ -208,6 +208,8 @@ SIGNATURES = {
     "pg_ntt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint32, C.c_uint32, _P(Scalar), _P(Scalar), C.c_void_p]),
     "pg_quotient": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar),
                               _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_quotient_blinded": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar),
+                                      _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_poly_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p]),
     "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_msm_segmented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(C.c_uint64), C.c_uint64,

@@ -395,16 +395,18 @@ class StandardComposer:
     def _padded_n(self, padded_n: int | None) -> int:
         return padded_n or 1 << max(0, (self.circuit_size() - 1).bit_length())
 
-    def wire_polynomials(self, padded_n: int | None = None) -> torch.Tensor:
+    def wire_polynomials(self, padded_n: int | None = None, tail: int = 0) -> torch.Tensor:
         """the four wire polynomials (w_l, w_r, w_o, w_4) as int64[4, padded_n, 4] coefficients: the wire values zero-padded to
-        the domain and interpolated in one call (the prover's round 1 without its blinding).  padded_n: a power of two >=
-        circuit_size, by default the next one."""
+        the domain and interpolated in one call (the prover's round 1 before its blinding).  padded_n: a power of two >=
+        circuit_size, by default the next one.  tail: that many zero rows behind every column (int64[4, padded_n + tail, 4]; the
+        first padded_n rows are transformed in place), the room Engine.blind needs."""
         n, padded_n = self.circuit_size(), self._padded_n(padded_n)
         assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
-        x = torch.zeros((4, padded_n, 4), dtype=torch.int64, device=self.engine.device)
+        x = torch.zeros((4, padded_n + tail, 4), dtype=torch.int64, device=self.engine.device)
         fc = _lib.FullColumnsC(w_l_value=x[0].data_ptr(), w_r_value=x[1].data_ptr(), w_o_value=x[2].data_ptr(), w_4_value=x[3].data_ptr())
         _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
-        return self.engine.ifft(x, inplace=True)
+        self.engine.ifft(x[:, :padded_n], inplace=True)
+        return x
 
     def sigma_polynomials(self, padded_n: int | None = None) -> torch.Tensor:
         """the four sigma polynomials as int64[4, padded_n, 4] coefficients: the ifft of sigma_evaluations(permutation(padded_n))
@@ -471,11 +473,13 @@ class StandardComposer:
 
     NON_ARITHMETIC_SELECTORS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
 
-    def prover_polynomials(self, beta, gamma, padded_n: int | None = None) -> dict:
+    def prover_polynomials(self, beta, gamma, padded_n: int | None = None, tail: int = 0) -> dict:
         """the 17 inputs of Engine.quotient as coefficients over the padded domain, keyed by its arguments: wires
         (int64[4, padded_n, 4]), z (permutation_polynomial), sigmas (sigma_polynomials), selectors (the seven of
         Engine.QUOTIENT_SELECTORS) and pi (public_input_polynomial).  Nothing refers to the composer afterwards, so it may be
-        closed before the quotient is computed.  Raises ValueError if a selector of the widgets the quotient leaves out (range,
+        closed before the quotient is computed.  tail: that many zero rows behind every wire column and behind z (wires
+        int64[4, padded_n + tail, 4], z int64[padded_n + tail, 4]; their first padded_n rows are transformed in place), the room
+        Engine.blind needs; 0 by default.  Raises ValueError if a selector of the widgets the quotient leaves out (range,
         logic, fixed- and variable-base group additions) is not zero, and NonExistingInverse as the grand product does."""
         n, padded_n = self.circuit_size(), self._padded_n(padded_n)
         assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
@@ -493,15 +497,16 @@ class StandardComposer:
         for name in Columns.SCALAR_COLS:
             sel[names.index(name), :n] = getattr(cols, name)
         del cols
-        wires = torch.zeros((4, padded_n, 4), dtype=torch.int64, device=dev)
+        wires = torch.zeros((4, padded_n + tail, 4), dtype=torch.int64, device=dev)
         fc = _lib.FullColumnsC(q_4=sel[names.index("q_4")].data_ptr(), q_arith=sel[names.index("q_arith")].data_ptr(),
                                **{f"w_{w}_value": wires[j].data_ptr() for j, w in enumerate("lro4")})
         _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
         self.engine.ifft(sel, inplace=True)
         sigma = self.permutation(padded_n)
-        z, _ = self.engine.permutation_product([wires[j, :n] for j in range(4)], sigma, beta, gamma)
-        self.engine.ifft(z, inplace=True)
-        self.engine.ifft(wires, inplace=True)
+        z = torch.zeros((padded_n + tail, 4), dtype=torch.int64, device=dev) if tail else None
+        z, _ = self.engine.permutation_product([wires[j, :n] for j in range(4)], sigma, beta, gamma, z_out=z)
+        self.engine.ifft(z[:padded_n], inplace=True)
+        self.engine.ifft(wires[:, :padded_n], inplace=True)
         sigmas = self.engine.sigma_evaluations(sigma)
         del sigma
         self.engine.ifft(sigmas, inplace=True)
@@ -512,15 +517,20 @@ class StandardComposer:
         """the quotient polynomial t as int64[4, padded_n, 4] (t_lo, t_mid, t_hi, t_4th): Engine.quotient of prover_polynomials()"""
         return self.engine.quotient(**self.prover_polynomials(beta, gamma, padded_n), alpha=alpha, beta=beta, gamma=gamma)
 
-    def prove(self, ck, label=b"plonk", preprocessed: dict | None = None, timings: dict | None = None):
+    def prove(self, ck, label=b"plonk", preprocessed: dict | None = None, timings: dict | None = None, blinding=None):
         """a PLONK proof (proof.Proof) of the circuit as it stands, padded to the next power of two, under the CommitKey ck:
         dusk-plonk 0.8's Prover::prove [DEP-RECALL] with the transcript label `label` (Prover::default()'s is b"plonk").
         preprocessed: the dict of preprocessed_commitments(ck), so that proving the same circuit again (after clear_witness)
         does not repeat its 15 MSMs.  timings: a dict that receives each phase's milliseconds (the device synchronised between
-        phases).  Without blinding the proof is NOT zero-knowledge.  Raises PolynomialDegreeTooLarge when the
-        padded circuit exceeds the key, ValueError for the widgets the quotient leaves out."""
+        phases).  blinding: None (the default, which keeps the proofs of earlier versions byte for byte) gives a proof that is
+        sound but NOT zero-knowledge; True blinds the wire polynomials and the grand product with 11 fresh scalars from the
+        operating system's generator (the PLONK paper's rounds 1 and 2), which makes the proof
+        zero-knowledge up to the quotient's parts, which are not blinded; a sequence of 11 integers below r (a1 a0 b1 b0 c1 c0 d1
+        d0 z2 z1 z0) is used as given, for tests.  The proof is an ordinary 1040-byte proof either way.  A blinded proof needs a
+        circuit padded to at least 8 rows (ValueError) and a key of at least padded_n + 8 powers.  Raises PolynomialDegreeTooLarge
+        when the padded circuit exceeds the key, ValueError for the widgets the quotient leaves out."""
         from .proof import prove
-        return prove(self, ck, label, preprocessed, timings)
+        return prove(self, ck, label, preprocessed, timings, blinding)
 
 @dataclass
 class AllocatedScalar:

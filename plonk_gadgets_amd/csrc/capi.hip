@@ -1382,15 +1382,14 @@ void quotient_step(const pg_engine *e, const pg::QuotientChunk &A, hipStream_t s
     hipLaunchKernelGGL(pg::quotient_step_kernel<OP>, dim3(grid), dim3(pg::kThreads), 0, st, A);
 }
 
-}  // namespace
-
-extern "C" {
-
-pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
-                      const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
-                      pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
+// pg_quotient (blinded = false: today's launches, nothing else) and pg_quotient_blinded (w[j] of n + 2 rows, z of n + 3, d_t of
+// 4n + 8: QS_BLIND after each chunk's five wire / z transforms and quotient_top_kernel after the combine)
+pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
+                           const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
+                           pg_scalar *d_t, pg_scalar *d_scratch, void *stream, bool blinded) {
     if (!e || !p || !k) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (log2_n > 30) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n > 30");
+    if (blinded && log2_n < 3) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n < 3: the blinders' rows would meet the top rows");
     const uint32_t m = log2_n;
     const uint64_t n = 1ull << m, col_bytes = n * sizeof(pg_scalar);
     // the inputs in the order the chunks consume them; pi (the last) may be NULL
@@ -1411,11 +1410,14 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
         return fail(PG_ERR_INVALID_ARGUMENT, "omega_4n is not a primitive 4n-th root of unity");
     if (pg::fr_is_zero(g) || pg::fr_eq(fr_sqr_times(g, m + 2), pg::fr_one()))
         return fail(PG_ERR_INVALID_ARGUMENT, "coset_gen is zero or coset_gen^(4n) = 1: the coset meets H");
-    const uint64_t t_bytes = 4 * col_bytes, s_bytes = PG_QUOTIENT_SCRATCH_COLS * col_bytes;
+    const uint64_t t_bytes = 4 * col_bytes + (blinded ? 8 * sizeof(pg_scalar) : 0), s_bytes = PG_QUOTIENT_SCRATCH_COLS * col_bytes;
     if (overlaps(d_t, t_bytes, d_scratch, s_bytes)) return fail(PG_ERR_INVALID_ARGUMENT, "d_t overlaps d_scratch");
-    for (const pg_scalar *x : in)
-        if (x && (overlaps(d_t, t_bytes, x, col_bytes) || overlaps(d_scratch, s_bytes, x, col_bytes)))
+    for (int i = 0; i < 17; i++) {
+        const pg_scalar *x = in[i];
+        const uint64_t x_bytes = col_bytes + (blinded && i < 5 ? (i < 4 ? 2 : 3) * sizeof(pg_scalar) : 0);  // the tails of w[j] and z
+        if (x && (overlaps(d_t, t_bytes, x, x_bytes) || overlaps(d_scratch, s_bytes, x, x_bytes)))
             return fail(PG_ERR_INVALID_ARGUMENT, "d_t or d_scratch overlaps an input polynomial");
+    }
     hipStream_t st = static_cast<hipStream_t>(stream);
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
@@ -1436,6 +1438,8 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
     for (int j = 0; j < 4; j++) A.beta_k[j] = pg::fr_mul(A.beta, to_fr(&k[j]));
     A.n_fr = pg::fr_from_u64(n);
     const pg::Fr alpha2 = pg::fr_mul(A.alpha, A.alpha);
+    if (blinded)
+        for (int i = 0; i < 5; i++) A.tail[i] = reinterpret_cast<const uint4 *>(in[i]) + 2 * n;
     pg::Fr g_j = g, zeta_jn = pg::fr_one();  // g zeta^j, zeta^(jn)
     for (uint32_t j = 0; j < 4; j++) {
         // coset-forward transform of input i into scratch column c, with generator g_j
@@ -1448,6 +1452,10 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
         A.alpha2_c = pg::fr_mul(alpha2, c_j);
         A.c_inv = pg::fr_invert_or_zero(c_j);
         for (int i = 0; i < 5; i++) PG_TRY(fwd(i, (uint32_t)i));  // a, b, c, d, z: resident for the chunk
+        if (blinded) {  // QS_BLIND
+            A.xn = pg::fr_mul(g_n, zeta_jn);
+            hipLaunchKernelGGL(pg::quotient_blind_kernel, dim3(grid_of(e, n, 8)), dim3(pg::kThreads), 0, st, A);
+        }
         quotient_step<pg::QS_PERM_NUM>(e, A, st);
         PG_TRY(fwd(5, 5)); PG_TRY(fwd(6, 6)); PG_TRY(fwd(7, 7));  // q_m, q_l, q_r
         quotient_step<pg::QS_GATE1>(e, A, st);
@@ -1473,8 +1481,44 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
     Cb.scale[0] = pg::fr_invert_or_zero(pg::fr_from_u64(4));
     for (int j = 1; j < 4; j++) Cb.scale[j] = pg::fr_mul(Cb.scale[j - 1], g_n_inv);
     hipLaunchKernelGGL(pg::quotient_combine_kernel, dim3(grid_of(e, n, 8)), dim3(pg::kThreads), 0, st, Cb);
+    if (blinded) {
+        pg::QuotientTop Tp{};
+        for (int j = 0; j < 4; j++) {
+            Tp.w[j] = reinterpret_cast<const uint4 *>(p->w[j]);
+            Tp.sigma[j] = reinterpret_cast<const uint4 *>(p->sigma[j]);
+        }
+        Tp.z = reinterpret_cast<const uint4 *>(p->z);
+        Tp.t = T;
+        Tp.n = n;
+        Tp.alpha = A.alpha;
+        Tp.beta = A.beta;
+        Tp.g4n = fr_sqr_times(g_n, 2);
+        // omega^(n + 2 - d) = omega^2, omega, 1, omega^-1, ..., omega^-4
+        const pg::Fr omega_inv = pg::fr_invert_or_zero(omega);
+        Tp.zw[2] = pg::fr_one();
+        Tp.zw[1] = omega;
+        Tp.zw[0] = pg::fr_mul(omega, omega);
+        for (uint32_t d = 3; d < pg::kQTop; d++) Tp.zw[d] = pg::fr_mul(Tp.zw[d - 1], omega_inv);
+        hipLaunchKernelGGL(pg::quotient_top_kernel, dim3(1), dim3(pg::kQTopLanes), 0, st, Tp);
+    }
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
+                      const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
+                      pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
+    return quotient_enqueue(e, log2_n, p, alpha, beta, gamma, omega_4n, k, coset_gen, d_t, d_scratch, stream, false);
+}
+
+pg_status pg_quotient_blinded(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha,
+                              const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4],
+                              const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
+    return quotient_enqueue(e, log2_n, p, alpha, beta, gamma, omega_4n, k, coset_gen, d_t, d_scratch, stream, true);
 }
 
 pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_cols, uint64_t col_stride, uint64_t n,

@@ -24,6 +24,17 @@
 // never zero once the host has checked g^(4n) != 1, so nothing on the device can fail.
 // No scratch memory, no LDS; 64-bit indices wherever one can reach 4n.
 //
+// The blinded quotient (pg_quotient_blinded): wire j has n + 2 coefficients, w_j = w_j0 + (b1 X + b0)(X^n - 1),
+// and z has n + 3, z = z0 + (b2 X^2 + b1 X + b0)(X^n - 1), each a plain coefficient array whose rows n.. (the tail) hold the
+// blinders.  On chunk j, x^n = c_j + 1 is a constant, so the values of a blinded column are the n-point coset transform of its
+// rows 0..n-1 plus (c_j + 1) tail(x): step QS_BLIND (quotient_blind_kernel) adds that to scratch columns 0..4 after their
+// transforms and before QS_PERM_NUM, and the six steps above run as they are.  N now has degree <= 5n + 6 and t = N / (X^n - 1)
+// degree <= 4n + 6, so the 4n points give t~ = t mod (X^(4n) - g^(4n)): t~[k] = t[k] + g^(4n) t[4n + k] for k < 7.  With
+// t (X^n - 1) = N, t[4n + i] = N[5n + i] = T_i (i < 7, n >= 7), and only the two permutation products reach degree 5n: their top
+// seven coefficients are the truncated products of the top seven coefficients of their five factors (rows n+2..n-4 of z, times
+// omega^row for z(omega X); rows n+1..n-5 of w_j, plus beta sigma_j from row n-1 down; beta k_j X + gamma lie below for n >= 8).
+// quotient_top_kernel does that on one lane after the combine: t[4n + i] = T_i, t[4n + 7] = 0, t[k] -= g^(4n) T_k.
+//
 // The evaluation (pg_poly_evaluate): sum_{i < n} c_i x^i for n_cols columns at a stride, any n from 1 to 2^32.  A segment of
 // kEvalSeg points per workgroup step: lane t reads points s + 256 k + t (coalesced) and runs Horner along them (acc = acc x^256
 // + c: one multiplication per coefficient), multiplies by x^t (a 256-entry table) and the workgroup sums the lanes in LDS; lane 0
@@ -48,6 +59,7 @@ enum : int {
     QS_GATE3 = 3,     // t  += q_arith (s5 + q_c)                                       (s6 = q_c, s7 = q_arith)
     QS_PERM1 = 4,     // t  += PI (if any);  s6 = (a + beta sigma_1 + gamma)(b + beta sigma_2 + gamma)   (s5 = PI, s6, s7 = sigma_1, _2)
     QS_PERM2 = 5,     // t  = (t - alpha s6 (c + beta sigma_3 + gamma)(d + beta sigma_4 + gamma) z(omega x)) c_j^-1   (s5, s7 = sigma_3, _4)
+    QS_BLIND = 6,     // (pg_quotient_blinded only, before QS_PERM_NUM; quotient_blind_kernel)  s0..s4 += x^n tail(x)
 };
 
 struct QuotientChunk {
@@ -61,6 +73,9 @@ struct QuotientChunk {
     Fr n_fr;              // n as a field element
     Fr alpha2_c;          // alpha^2 c_j
     Fr c_inv;             // c_j^-1
+    // QS_BLIND alone reads these (pg_quotient leaves them zero)
+    const uint4 *tail[5]; // rows n.. of the caller's a, b, c, d (two rows each) and z (three)
+    Fr xn;                // x^n = c_j + 1 on the chunk
 };
 
 __device__ __forceinline__ Fr q_col(const QuotientChunk &A, uint32_t c, uint64_t i) { return pp_load(A.s, c * A.n + i); }
@@ -133,6 +148,27 @@ __global__ __launch_bounds__(kThreads) void quotient_step_kernel(const QuotientC
     }
 }
 
+// QS_BLIND: s_j[i] += x^n (h1 x + h0) for the wires (j < 4) and s_4[i] += x^n ((h2 x + h1) x + h0) for z, h = the tail rows, which
+// every lane reads once and multiplies by x^n
+__global__ __launch_bounds__(kThreads) void quotient_blind_kernel(const QuotientChunk A) {
+    Fr h[4][2], hz[3];
+#pragma unroll
+    for (uint32_t j = 0; j < 4; j++) {
+        h[j][0] = fr_mul(A.xn, pp_load(A.tail[j], 0));
+        h[j][1] = fr_mul(A.xn, pp_load(A.tail[j], 1));
+    }
+#pragma unroll
+    for (uint32_t r = 0; r < 3; r++) hz[r] = fr_mul(A.xn, pp_load(A.tail[4], r));
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < A.n; i += (uint64_t)gridDim.x * kThreads) {
+        const Fr x = ntt_pow(A.x, i);
+#pragma unroll
+        for (uint32_t j = 0; j < 4; j++)
+            pp_store(A.s, j * A.n + i, fr_add(q_col(A, j, i), fr_add(fr_mul(h[j][1], x), h[j][0])));
+        const Fr tz = fr_add(fr_mul(fr_add(fr_mul(hz[2], x), hz[1]), x), hz[0]);
+        pp_store(A.s, 4 * A.n + i, fr_add(q_col(A, 4, i), tz));
+    }
+}
+
 // the inverse 4-point DFT across the chunks, per k0 < n, in place: r_j = t[j n + k0] -> t[k0 + n k1] = scale[k1] sum_j iota^(j k1) r_j,
 // iota = zeta^-n (iota^2 = -1), scale[k1] = 4^-1 g^(-n k1)
 struct QuotientCombine {
@@ -150,6 +186,65 @@ __global__ __launch_bounds__(kThreads) void quotient_combine_kernel(const Quotie
         pp_store(A.t, 2 * A.n + i, fr_mul(fr_sub(e0, o0), A.scale[2]));
         pp_store(A.t, 3 * A.n + i, fr_mul(fr_sub(e1, o1), A.scale[3]));
     }
+}
+
+// the seven coefficients of the blinded quotient that 4n points cannot hold.  A factor is its top seven coefficients, highest
+// first (f[d] = the coefficient d below its degree); a product's top seven are then p[d] = sum_{d1 <= d} a[d1] b[d - d1].
+constexpr uint32_t kQTop = 7;
+constexpr uint32_t kQTopLanes = 64;  // one wave; lane 0 works
+struct QuotientTop {
+    const uint4 *w[4], *sigma[4], *z;  // the caller's inputs: n + 2, n and n + 3 rows
+    uint4 *t;                          // 4n + 8 rows
+    uint64_t n;
+    Fr alpha, beta, g4n;               // g4n = g^(4n)
+    Fr zw[kQTop];                      // omega^(n + 2 - d): z(omega X)'s coefficient d below the top is z's times this
+};
+
+// acc = the top seven of acc * b, in place: p[d] needs acc[0..d] only, so d runs downwards
+__device__ __forceinline__ void quotient_top_mul(Fr (&acc)[kQTop], const Fr (&b)[kQTop]) {
+#pragma unroll
+    for (int d = (int)kQTop - 1; d >= 0; d--) {
+        Fr p = fr_mul(acc[0], b[d]);
+#pragma unroll
+        for (int d1 = 1; d1 <= d; d1++) p = fr_add(p, fr_mul(acc[d1], b[d - d1]));
+        acc[d] = p;
+    }
+}
+
+// one working lane.  First T_i = N[5n + i] = alpha (P[6 - i] - P'[6 - i]) into t[4n + i], P = the top of z prod_j w_j (side 0)
+// and P' = the top of z(omega X) prod_j (w_j + beta sigma_j) (side 1); then t[k] -= g^(4n) T_k.  It runs after the combine.
+__global__ __launch_bounds__(kQTopLanes) void quotient_top_kernel(const QuotientTop A) {
+    if (blockIdx.x | threadIdx.x) return;
+    const uint64_t n = A.n;
+#pragma unroll 1
+    for (uint32_t side = 0; side < 2; side++) {
+        Fr acc[kQTop];
+#pragma unroll
+        for (uint32_t d = 0; d < kQTop; d++) {
+            acc[d] = pp_load(A.z, n + 2 - d);
+            if (side) acc[d] = fr_mul(acc[d], A.zw[d]);
+        }
+#pragma unroll 1
+        for (uint32_t j = 0; j < 4; j++) {
+            const uint4 *w = A.w[j], *sg = A.sigma[j];
+            Fr b[kQTop];
+#pragma unroll
+            for (uint32_t d = 0; d < kQTop; d++) {
+                b[d] = pp_load(w, n + 1 - d);
+                if (side && d >= 2) b[d] = fr_add(b[d], fr_mul(A.beta, pp_load(sg, n + 1 - d)));
+            }
+            quotient_top_mul(acc, b);
+        }
+#pragma unroll
+        for (uint32_t d = 0; d < kQTop; d++) {
+            const uint64_t row = 4 * n + (kQTop - 1 - d);
+            const Fr v = fr_mul(A.alpha, acc[d]);
+            pp_store(A.t, row, side ? fr_sub(pp_load(A.t, row), v) : v);
+        }
+    }
+    pp_store(A.t, 4 * n + kQTop, fr_zero());
+#pragma unroll 1
+    for (uint32_t k = 0; k < kQTop; k++) pp_store(A.t, k, fr_sub(pp_load(A.t, k), fr_mul(A.g4n, pp_load(A.t, 4 * n + k))));
 }
 
 // ---- evaluation at a point ----------------------------------------------------------------------------------------------------

@@ -458,9 +458,10 @@ class Engine:
             raise PgError(st, "pg_sigma_evaluations")
         return out
 
-    def permutation_product(self, wire_values, sigma: torch.Tensor, beta, gamma, omega=None, k=DEFAULT_K):
+    def permutation_product(self, wire_values, sigma: torch.Tensor, beta, gamma, omega=None, k=DEFAULT_K, z_out=None):
         """PLONK's copy-permutation grand product -> (z int64[padded_n, 4], wrap BlsScalar): z[i] = prod_{r < i} num_r / den_r,
-        wrap = the product of all padded_n ratios (one iff the wire values are constant on sigma's cycles).  wire_values: four
+        wrap = the product of all padded_n ratios (one iff the wire values are constant on sigma's cycles); z_out: an
+        int64[>= padded_n, 4] tensor whose first padded_n rows receive z (it is returned whole), else one is made.  wire_values: four
         int64[n_values, 4] tensors (the w_l / w_r / w_o / w_4 values of StandardComposer.materialize), rows >= n_values read as 0.
         Raises NonExistingInverse when a denominator is zero."""
         padded_n, om, ks = self._domain(sigma, omega, k)
@@ -469,7 +470,12 @@ class Engine:
         for w in wire_values:
             self._check_scalars(w, n_values)
         ptrs = (C.c_void_p * 4)(*[w.data_ptr() for w in wire_values])
-        z = torch.empty((padded_n, 4), dtype=torch.int64, device=self.device)
+        if z_out is None:
+            z = torch.empty((padded_n, 4), dtype=torch.int64, device=self.device)
+        else:
+            z = z_out
+            if not (self._rows(z) and z.dim() == 2 and z.shape[0] >= padded_n):
+                raise ValueError(f"z_out must be int64[>= {padded_n}, 4] on the device with contiguous rows")
         wrap = torch.empty((1, 4), dtype=torch.int64, device=self.device)
         st = self._lib.pg_permutation_product(self._h, padded_n, ptrs, n_values, sigma.data_ptr(), C.byref(om.c), ks,
                                               C.byref(_field(beta).c), C.byref(_field(gamma).c), z.data_ptr(), wrap.data_ptr(),
@@ -572,6 +578,60 @@ class Engine:
         if st != 0:
             raise PgError(st, "pg_quotient")
         return out
+
+    def quotient_blinded(self, wires, z, sigmas, selectors: dict, pi=None, *, alpha, beta, gamma, omega_4n=None, k=DEFAULT_K,
+                         g=DEFAULT_COSET_GENERATOR, scratch=None) -> torch.Tensor:
+        """the quotient polynomial of BLINDED wire and permutation polynomials (pg_quotient_blinded) as one
+        int64[4n + 8, 4]: the prover's parts are the views [0:n], [n:2n], [2n:3n] and [3n:4n + 8] (t_4th has n + 8 rows, the last
+        one zero).  wires: int64[4, n + 2, 4] or four int64[n + 2, 4] (views of longer columns will do), z: int64[n + 3, 4], blinded
+        as blind() blinds them; everything else as for quotient(), n = 2^m >= 8 the length of the sigmas."""
+        polys = [wires[j] for j in range(4)] + [z] + [sigmas[j] for j in range(4)] + [selectors[s] for s in self.QUOTIENT_SELECTORS]
+        n = polys[5].shape[0]
+        if n < 8 or n & (n - 1) or n > 1 << 30:
+            raise ValueError(f"n = {n} must be a power of two from 2^3 to 2^30")
+        for i, t in enumerate(polys + ([] if pi is None else [pi])):
+            rows = n + (2 if i < 4 else 3 if i == 4 else 0)
+            if not (self._rows(t) and t.dim() == 2 and t.shape[0] == rows):
+                raise ValueError(f"the wires must be int64[{n + 2}, 4], z int64[{n + 3}, 4] and every other input int64[{n}, 4], on "
+                                 "the device with contiguous rows")
+        log2_n = n.bit_length() - 1
+        if scratch is None:
+            scratch = torch.empty((8, n, 4), dtype=torch.int64, device=self.device)
+        elif not (self._rows(scratch) and scratch.is_contiguous() and scratch.numel() >= 8 * n * 4):
+            raise ValueError("scratch must be a contiguous int64 tensor of at least 8 x n x 4 elements")
+        out = torch.empty((4 * n + 8, 4), dtype=torch.int64, device=self.device)
+        p = _lib.QuotientPolysC()
+        for j in range(4):
+            p.w[j] = polys[j].data_ptr()
+            p.sigma[j] = polys[5 + j].data_ptr()
+        p.z = polys[4].data_ptr()
+        for i, s in enumerate(self.QUOTIENT_SELECTORS):
+            setattr(p, s, polys[9 + i].data_ptr())
+        p.pi = None if pi is None else pi.data_ptr()
+        zeta = domain_generator(log2_n + 2) if omega_4n is None else _field(omega_4n)
+        ks = (_lib.Scalar * 4)(*[_field(x).c for x in k])
+        st = self._lib.pg_quotient_blinded(self._h, log2_n, C.byref(p), C.byref(_field(alpha).c), C.byref(_field(beta).c),
+                                           C.byref(_field(gamma).c), C.byref(zeta.c), ks, C.byref(_field(g).c), out.data_ptr(),
+                                           scratch.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_quotient_blinded")
+        return out
+
+    def blind(self, poly_ext: torch.Tensor, n: int, blinders) -> torch.Tensor:
+        """poly_ext: int64[>= n + len(blinders), 4] on the device, rows 0..n-1 an interpolated polynomial and the rows behind them
+        zero; blinders: two (a wire: b1, b0) or three (z: b2, b1, b0) scalars, highest power first.  In place, poly_ext becomes
+        p + (sum_k b_k X^k)(X^n - 1): rows n.. get the blinders and the low rows lose them (4 rows change for a wire, 6 for z:
+        through the host).  The values on the n-point domain do not change.  Returns poly_ext."""
+        b = [_field(x) for x in reversed(list(blinders))]  # b0, b1, ...
+        c = len(b)
+        if not (self._rows(poly_ext) and poly_ext.dim() == 2 and n >= c and poly_ext.shape[0] >= n + c):
+            raise ValueError(f"poly_ext must be int64[>= n + {c}, 4] on the device with contiguous rows")
+        low = poly_ext[:c].cpu().tolist()
+        rows = [(BlsScalar.from_limbs([int(x) & (2**64 - 1) for x in r]) - bi).limbs() for r, bi in zip(low, b)]
+        signed = lambda limbs: [x - (1 << 64) if x >> 63 else x for x in limbs]
+        poly_ext[:c] = torch.tensor([signed(r) for r in rows], dtype=torch.int64).to(self.device)
+        poly_ext[n:n + c] = torch.tensor([signed(bi.limbs()) for bi in b], dtype=torch.int64).to(self.device)
+        return poly_ext
 
     def evaluate(self, polys: torch.Tensor, point) -> list:
         """the polynomials at a point (pg_poly_evaluate, the prover's round 4): polys int64[n, 4] or int64[c, n, 4] coefficients

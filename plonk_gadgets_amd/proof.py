@@ -2,10 +2,16 @@
 (interpolation, the grand product, the quotient, evaluations, commitments and the openings of csrc/opening.hpp), with the
 Fiat-Shamir transcript of transcript.py on the host.  DESIGN section 3.12.
 
-Blinding is left out: the proof is sound but NOT zero-knowledge.  The arithmetic gate, the public inputs and
-the copy permutation are proven; circuits that use the range, logic or group-addition widgets are refused (prover_polynomials)."""
+Blinding is off by default, which keeps the proofs of earlier versions byte for byte: such a proof is sound
+but NOT zero-knowledge.  prove(..., blinding=True) blinds the four wire polynomials and the grand product with 11 fresh scalars,
+w_j + (b1 X + b0)(X^n - 1) and z + (b2 X^2 + b1 X + b0)(X^n - 1) (the PLONK paper's rounds 1 and 2; dusk-plonk 0.8 has none), so
+that the commitments and evaluations a proof reveals are those of blinded polynomials; the quotient's parts are not blinded
+separately (the paper's optional b10, b11 are left out).  The verifier does not change: a blinded proof is an ordinary proof.  The
+arithmetic gate, the public inputs and the copy permutation are proven; circuits that use the range, logic or group-addition
+widgets are refused (prover_polynomials)."""
 from __future__ import annotations
 
+import secrets
 import time
 from dataclasses import dataclass, fields
 
@@ -132,13 +138,38 @@ class _Phases:
             self.t = t
 
 
-def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None = None) -> Proof:
+BLINDERS = 11  # a1 a0 b1 b0 c1 c0 d1 d0 z2 z1 z0
+TAIL = 8       # zero rows behind every blinded column: the quotient's fourth part has n + 8 rows, and round 5 opens over n + 8
+
+
+def _blinders(blinding):
+    """prove's `blinding` -> None or 11 ints below r"""
+    if blinding is None or blinding is False:
+        return None
+    if blinding is True:
+        return [secrets.randbelow(R) for _ in range(BLINDERS)]
+    b = [int(x) for x in blinding]
+    if len(b) != BLINDERS:
+        raise ValueError(f"blinding must be None, True or {BLINDERS} integers (a1 a0 b1 b0 c1 c0 d1 d0 z2 z1 z0), not {len(b)}")
+    if any(not 0 <= x < R for x in b):
+        raise ValueError("a blinder is not reduced below r")
+    return b
+
+
+def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None = None, blinding=None) -> Proof:
     """StandardComposer.prove: see there"""
     eng = composer.engine
     padded_n = composer._padded_n(None)
     m = padded_n.bit_length() - 1
+    bl = _blinders(blinding)
+    tail = 0 if bl is None else TAIL
+    if bl is not None and padded_n < 8:
+        raise ValueError(f"padded_n = {padded_n}: a blinded proof needs a circuit padded to at least 8 rows")
     if padded_n > ck.powers.shape[0]:
         raise PolynomialDegreeTooLarge(f"padded_n = {padded_n} > the key's {ck.powers.shape[0]} powers")
+    if padded_n + tail > ck.powers.shape[0]:
+        raise PolynomialDegreeTooLarge(f"a blinded proof needs padded_n + {TAIL} = {padded_n + TAIL} powers (the quotient's fourth "
+                                       f"part has n + {TAIL} coefficients); the key has {ck.powers.shape[0]}")
     ph = _Phases(timings, eng.device)
     if preprocessed is None:
         preprocessed = composer.preprocessed_commitments(ck, padded_n)
@@ -150,9 +181,12 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
     S = BlsScalar.from_int
 
     # round 1: the wire polynomials
-    wires = composer.wire_polynomials(padded_n)
+    wires = composer.wire_polynomials(padded_n, tail)
+    if bl is not None:
+        for j in range(4):
+            eng.blind(wires[j], padded_n, bl[2 * j:2 * j + 2])
     ph.mark("round1_interpolate")
-    w_comm = ck.commit(wires)
+    w_comm = ck.commit(wires[:, :padded_n + 2] if tail else wires)
     del wires
     ph.mark("round1_msm")
     for lab, c in zip((b"w_l", b"w_r", b"w_o", b"w_4"), w_comm):
@@ -162,17 +196,29 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
     gamma = tr.challenge_int(b"gamma")
 
     # round 2: the grand product (prover_polynomials also gives round 3's inputs)
-    pp = composer.prover_polynomials(S(beta), S(gamma), padded_n)
+    pp = composer.prover_polynomials(S(beta), S(gamma), padded_n, tail)
+    if bl is not None:
+        for j in range(4):
+            eng.blind(pp["wires"][j], padded_n, bl[2 * j:2 * j + 2])
+        eng.blind(pp["z"], padded_n, bl[8:11])
     ph.mark("round2_polynomials")
-    z_comm = ck.commit(pp["z"])
+    z_comm = ck.commit(pp["z"][:padded_n + 3] if tail else pp["z"])
     ph.mark("round2_msm")
     tr.append_commitment(b"z", z_comm)
     alpha = tr.challenge_int(b"alpha")
 
     # round 3: the quotient
-    t = eng.quotient(**pp, alpha=S(alpha), beta=S(beta), gamma=S(gamma))
-    ph.mark("round3_quotient")
-    t_comm = ck.commit(t)
+    if bl is None:
+        t = eng.quotient(**pp, alpha=S(alpha), beta=S(beta), gamma=S(gamma))
+        ph.mark("round3_quotient")
+        t_comm = ck.commit(t)
+    else:
+        # t_1, t_2, t_3 of n rows and t_4 of n + 8, views of one int64[4n + 8, 4]
+        tq = eng.quotient_blinded([pp["wires"][j, :padded_n + 2] for j in range(4)], pp["z"][:padded_n + 3], pp["sigmas"],
+                                  pp["selectors"], pp["pi"], alpha=S(alpha), beta=S(beta), gamma=S(gamma))
+        ph.mark("round3_quotient")
+        t = [tq[j * padded_n:(j + 1) * padded_n] for j in range(3)] + [tq[3 * padded_n:]]
+        t_comm = ck.commit(tq[:3 * padded_n].view(3, padded_n, 4)) + [ck.commit(t[3])]
     ph.mark("round3_msm")
     for i, c in enumerate(t_comm):
         tr.append_commitment(b"t_%d" % (i + 1), c)
@@ -221,7 +267,18 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
     for key, tensor in zip(keys, opened):
         vi = vi * v % R
         put(key, tensor, vi)
-    w_xi, _ = eng.open([cols[k_] for k_ in cols], [mu[k_] for k_ in cols], xi)
+    if bl is None:
+        w_xi, _ = eng.open([cols[k_] for k_ in cols], [mu[k_] for k_ in cols], xi)
+    else:
+        # pg_poly_open wants one length for all its columns, and the witness is linear in them: the columns of n + 8 rows (t_4
+        # and the tail-padded wires and z) open together, the columns of n rows together, and the two witnesses add up
+        long_ = [k_ for k_ in cols if cols[k_].shape[0] == padded_n + TAIL]
+        short = [k_ for k_ in cols if cols[k_].shape[0] == padded_n]
+        assert len(long_) == 6 and len(long_) + len(short) == len(cols)
+        w_xi, _ = eng.open([cols[k_] for k_ in long_], [mu[k_] for k_ in long_], xi)
+        w_lo, _ = eng.open([cols[k_] for k_ in short], [mu[k_] for k_ in short], xi)
+        w_xi[:padded_n] = eng.combine([w_xi[:padded_n], w_lo], [1, 1])
+        del w_lo, tq
     del t, cols
     ph.mark("round5_open")
     w_z_comm = ck.commit(w_xi)
