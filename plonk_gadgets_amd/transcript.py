@@ -1,8 +1,12 @@
 """The prover's Fiat-Shamir transcript: Merlin (STROBE-128 over Keccak-f[1600]) in pure Python, with dusk-plonk 0.8's
 TranscriptProtocol on top [DEP-RECALL].  A proof feeds it a few hundred bytes, so it runs on the host.
 
-The permutation is pinned by tests/test_transcript.py (SHA3-256 and SHAKE128 sponges built on it equal hashlib's).  The STROBE
-and Merlin framing has no test vectors in this repository: its parity is unpinned, as DESIGN section 5 says of rows and limbs."""
+What tests/test_transcript.py pins: the permutation (SHA3-256 and SHAKE128 sponges built on it equal hashlib's); the STROBE and
+Merlin framing, by merlin's published vector and by an independent STROBE-128 (tests/strobe_model.py) that this one equals byte for
+byte and state for state with a block boundary on every kind of byte; and, through tests/test_sides_replay_host.py and
+tests/test_gpu_sides_replay.py, the table-driven replay of csrc/plonk_sides.hpp against this class from every seed position, on the
+host and on the device.  What is still unpinned: that dusk-plonk 0.8 appends these messages under these labels in this order is a
+recollection [DEP-RECALL]; no vector for it exists here."""
 from __future__ import annotations
 
 from .scalar import BlsScalar

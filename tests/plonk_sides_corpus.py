@@ -22,6 +22,8 @@ RINV = pow(1 << 256, -1, R)
 ROWS, PROOF = V.SIDES_ROWS, V.PROOF_BYTES
 EVAL_AT = 48 * len(COMMITMENTS)
 LABELS = (b"plonk", b"", bytes(range(150)), bytes(200 - i for i in range(200)))
+# a label of every length 0 .. 165: together they leave a key's seed at every position 0 .. 165 of the sponge's block
+SEED_LABELS = tuple(bytes((37 * i + 11 * n + 1) & 0xFF for i in range(n)) for n in range(166))
 
 
 class Ok:
@@ -46,6 +48,37 @@ def make_proof(seed):
     ks[3] = 0
     ks[2] = ks[1]
     return pg.Proof(*[point(k) for k in ks], *[pg.BlsScalar.from_int(rng.randrange(R)) for _ in EVALUATIONS])
+
+
+def seed_position_batch():
+    """one key of n = 2^12, one proof, public inputs on two rows, and the key's 166 records under SEED_LABELS: proof i of the batch
+    goes under record i -> (vk, proof bytes, public inputs, records)"""
+    vk = make_key(1 << 12, 0x5EED)
+    pi = {3: 0x1234_5678_9abc_def0, (1 << 12) - 1: R - 5}
+    return vk, make_proof(0x5EEE).to_bytes(), pi, [vk.record(Ok, lab) for lab in SEED_LABELS]
+
+
+def spread_rows(n: int, count: int, salt: int) -> dict:
+    """public inputs on `count` distinct rows of [0, n) -- the first and the last among them -- or on all n rows if n < count"""
+    count = min(count, n)
+    rows = {0, n - 1} if count > 1 else {0}
+    k = 0
+    while len(rows) < count:
+        rows.add((salt * 0x9E3779B97F4A7C15 + k * 0xD1B54A32D192ED03) % n)
+        k += 1
+    return {r: pow(7, salt + j + 1, R) for j, r in enumerate(sorted(rows)[:count])} if count else {}
+
+
+def extreme_batch(n_proofs=70):
+    """the smallest and the largest circuit (n = 1: log2 n = 0; n = 2^32: the largest pg_plonk_sides accepts) and n = 2^12,
+    interleaved, with ragged public inputs of 0, 1, 64 and 257 rows (n = 1 has the one row) across the lanes of a workgroup
+    -> (proof bytes, records, key indices, public inputs, [(vk, label)] per record)"""
+    keyed = [(make_key(1, 0xE0), SEED_LABELS[165]), (make_key(1 << 32, 0xE1), SEED_LABELS[137]), (make_key(1 << 12, 0xE2), LABELS[0])]
+    proofs = [make_proof(0xE10 + i).to_bytes() for i in range(3)]
+    index = [i % 3 for i in range(n_proofs)]
+    pis = [spread_rows(keyed[index[i]][0].n, (257, 64, 1, 0)[(i // 3) % 4], i) or None for i in range(n_proofs)]
+    assert {len(p or {}) for p in pis} == {0, 1, 64, 257}
+    return b"".join(proofs[(i // 4) % 3] for i in range(n_proofs)), [vk.record(Ok, lab) for vk, lab in keyed], index, pis, keyed
 
 
 def with_commitment(data: bytes, j: int, enc: bytes) -> bytes:

@@ -2,7 +2,10 @@
 corpus of tests/test_plonk_sides_host.py replicated to 1, 63, 64, 65 and 257 proofs (one lane short of a workgroup, one
 workgroup, one lane more, several): three keys of different n and label interleaved through d_key_index, ragged public inputs,
 every rejection class in every batch that has room for it, a key index past the table, and a scalar col_stride larger than 23 n.
-And every argument error leaves sentinel-filled outputs untouched."""
+And every argument error leaves sentinel-filled outputs untouched.  Two more batches, which tests/test_plonk_sides_host.py compares
+with verifier.sides on the host: 166 proofs under the 166 records whose seeds stand at every position of the sponge's block (three
+workgroups, every lane permuting at different bytes, rejected proofs among them), and the keys of n = 1 and n = 2^32 with public
+inputs of up to 257 rows."""
 import pytest
 import torch
 
@@ -67,6 +70,44 @@ def test_device_equals_host(engine, corpus, n):
     for col in (0, 1):
         at = 32 * ROWS * N_MAX * col
         assert got[col].tobytes() == h_scalars[at:at + 32 * ROWS * n], col
+
+
+def device_equals_host(engine, batch):
+    data, records, index, pis = batch
+    n = len(index)
+    st, h_bases, h_scalars, h_status, h_where = K.host_sides(data, records, index, pis)
+    assert st == 0
+    bases, scalars, status, where = engine.plonk_sides(*upload(engine, n, (data, records, index, pis, None)))
+    assert bytes(status.cpu().numpy()) == h_status and bytes(where.cpu().numpy()) == h_where
+    assert bases.cpu().numpy().tobytes() == h_bases
+    assert scalars.cpu().numpy().tobytes() == h_scalars
+    return h_status, h_where
+
+
+def test_a_seed_at_every_position_in_one_launch(engine):
+    """proof i under record i: workgroups of 64, 64 and 38 lanes, every lane's seed at another pos; one rejected proof of every
+    class among them (those lanes skip the sponge), a public input past n and a key index past the table"""
+    vk, proof, pi, records = K.seed_position_batch()
+    assert {rec[200] for rec in records} == set(range(166))
+    n = len(records)
+    proofs, index, pis = [proof] * n, list(range(n)), [pi] * n
+    enc = K.rejected_encodings()
+    for lane, (j, name) in zip((5, 63, 64, 130), ((0, "compressed-bit-clear"), (3, "x-not-below-p"), (6, "x-with-no-y"), (10, "outside-the-subgroup"))):
+        proofs[lane] = K.with_commitment(proof, j, enc[name][0])
+    proofs[40] = K.with_evaluation(proof, 9, R)
+    proofs[165] = K.with_evaluation(proof, 15, (1 << 256) - 1)
+    pis[100] = {1 << 12: 1}
+    index[127] = n
+    status, where = device_equals_host(engine, (b"".join(proofs), records, index, pis))
+    rejected = {5: (1, 0), 63: (1, 3), 64: (2, 6), 130: (3, 10), 40: (5, 9), 165: (5, 15), 100: (7, 0), 127: (8, 0)}
+    assert [(status[i], where[i]) for i in range(n)] == [rejected.get(i, (0, 0)) for i in range(n)]
+
+
+def test_the_smallest_and_largest_keys_with_long_public_inputs(engine):
+    data, records, index, pis, _ = K.extreme_batch()
+    assert sorted(rec[203] for rec in records) == [0, 12, 32] and {len(p or {}) for p in pis[:64]} == {0, 1, 64, 257}
+    status, _ = device_equals_host(engine, (data, records, index, pis))
+    assert status == bytes(len(index))
 
 
 def test_no_public_inputs_and_one_key_need_no_arrays(engine, corpus):

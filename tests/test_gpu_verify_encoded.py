@@ -4,12 +4,14 @@ The three circuits and the cases of tests/test_gpu_verify_each_segmented.py, bui
 a public input, both; honest, a spoiled evaluation, two and three coinciding commitments), and the off-curve case in bytes: a
 commitment whose x has no y, and one that is a curve point outside G1.  Batches of 1, 2, 17 and 65 with mixed keys and public
 inputs; exactly one pg_plonk_sides, one pg_msm_segmented, one pg_pairing_check and no pg_msm per call; bytes, tensors and Proof
-objects give the same answer; a batch rejected entirely before the pairing is all False."""
+objects give the same answer; a batch rejected entirely before the pairing is all False.  And real proofs under four labels that
+put the end of the sponge's first block after the seed on bytes the label b"plonk" never puts it on."""
 import pytest
 import torch
 
 import plonk_gadgets_amd as pg
 import plonk_sides_corpus as K
+import strobe_model as sm
 from plonk_gadgets_amd import verifier as V
 
 pytestmark = pytest.mark.gpu
@@ -25,7 +27,7 @@ def engine():
     e.close()
 
 
-def circuit(engine, ck, kind):
+def circuit(engine, ck, kind, label=b"plonk"):
     comp = pg.StandardComposer(engine, 1 << 12, 1 << 12)
     pi = {}
     if kind != 1:  # a range check: the ladder's selectors
@@ -45,17 +47,24 @@ def circuit(engine, ck, kind):
         assert pi
     pre = comp.preprocessed_commitments(ck)
     n = 1 << max(0, (comp.circuit_size() - 1).bit_length())
-    out = (comp.prove(ck, b"plonk", pre), pg.VerifierKey(n, pre), pi)
+    out = (comp.prove(ck, label, pre), pg.VerifierKey(n, pre), pi)
     comp.close()
     return out
 
 
 @pytest.fixture(scope="module")
-def world(engine):
-    """[(proof bytes, key, public inputs)], what verify says of each (False where the bytes are no Proof), the status
-    verify_encoded must give, the opening key"""
+def setup(engine):
     ck = pg.CommitKey.setup(engine, (1 << 12) - 1, S(TAU))
     ok = pg.OpeningKey.setup(engine, S(TAU))
+    yield ck, ok
+    ok.close()
+
+
+@pytest.fixture(scope="module")
+def world(engine, setup):
+    """[(proof bytes, key, public inputs)], what verify says of each (False where the bytes are no Proof), the status
+    verify_encoded must give, the opening key"""
+    ck, ok = setup
     three = [circuit(engine, ck, kind) for kind in range(3)]
     cases = [(p.to_bytes(), vk, pi) for p, vk, pi in three]
     spoiled = pg.Proof.from_bytes(cases[1][0])
@@ -78,8 +87,7 @@ def world(engine):
             verdicts.append(False)
     assert verdicts == [True, True, True, False, False, False, False, False, False]
     status = [(0, 0)] * 6 + [(2, 0), (3, 4), (0, 0)]
-    yield cases, verdicts, status, ok
-    ok.close()
+    return cases, verdicts, status, ok
 
 
 @pytest.fixture
@@ -137,3 +145,27 @@ def test_a_batch_rejected_before_the_pairing_is_all_false(engine, world, counted
                                     [cases[6][2], cases[7][2], None, {1 << 12: 1}], return_status=True)
     assert got == [False] * 4 and list(zip(st, wh)) == [(2, 0), (3, 4), (5, 5), (2, 0)]
     assert counted["pg_plonk_sides"] == 1 and counted["pg_msm"] == 0
+
+
+# what ends the first block after the key's seed (strobe_model.sides_phase0_classes) -> a label that puts it there
+BOUNDARY_LABELS = {"begin-first": b"plnk", "commitment-first": b"pk", "commitment-last": b"plonk-verifier", "length-0": b"plonk-v2"}
+
+
+def test_real_proofs_under_labels_that_end_a_block_where_the_others_do_not(engine, setup):
+    """the four labels of tests/plonk_sides_corpus.py end that block inside a message, on the last length byte or on a flags byte;
+    these four end it on begin_op's first framing byte, on the first and on the last byte of a commitment, and on the first byte
+    of a length word.  A proof verifies under its own label alone, and verify_encoded says what verify says."""
+    ck, ok = setup
+    labels = list(BOUNDARY_LABELS.values())
+    proved = [circuit(engine, ck, 2, lab) for lab in labels]
+    vk, pi = proved[0][1], proved[0][2]
+    assert all(v == vk and q == pi for _, v, q in proved)
+    old = set().union(*(sm.sides_phase0_classes(lab, vk.n) for lab in K.LABELS))  # (n travels as 8 bytes whatever it is)
+    for cls, lab in BOUNDARY_LABELS.items():
+        assert cls in sm.sides_phase0_classes(lab, vk.n) and cls not in old, cls
+    assert len({vk.record(ok, lab)[200] for lab in labels}) == 4  # four seed positions
+    pairs = [(i, j) for i in range(4) for j in range(4)]
+    data = b"".join(proved[i][0].to_bytes() for i, _ in pairs)
+    got, st, _ = pg.verify_encoded(data, vk, ok, pi, label=[labels[j] for _, j in pairs], return_status=True)
+    assert got == [i == j for i, j in pairs] and st == [0] * 16
+    assert [pg.verify(proved[i][0], vk, ok, pi, labels[j]) for i, j in pairs] == got

@@ -3,7 +3,8 @@
 The proofs are synthetic (tests/plonk_sides_corpus.py).  A proof's 23 rows are grouped by base limbs and their scalars summed mod
 r: the result must be the model's {point: [a, b]} exactly, zero entries ignored, in both columns.  That equality pins the
 transcript too: one wrong framing byte changes every challenge and with it every scalar.  Labels of 5, 0, 150 and 200 bytes put
-the seed's `pos` early, late and past a block boundary of the sponge."""
+the seed's `pos` early, late and past a block boundary of the sponge; the labels of every length 0 .. 165 (K.SEED_LABELS) put it at
+every one of the 166 positions, so that every byte of the first phase's operations ends a block under some label."""
 import ctypes as C
 
 import pytest
@@ -56,6 +57,32 @@ def test_rows_are_the_models_table(keys, proofs, n, label):
         proof = K.pg.Proof.from_bytes(proofs[k])
         want = [getattr(proof, f) for f in K.COMMITMENTS] + [keys[n].commitments[f] for f in V.SIDES_KEY_ROWS] + [K.Ok.g]
         assert [tuple(b[12 * r:12 * r + 12]) for r in range(ROWS)] == [p.limbs for p in want]
+
+
+def test_a_label_of_every_length_puts_the_seed_at_every_position():
+    """166 records of one key, proof i under record i, in one call"""
+    vk, proof, pi, records = K.seed_position_batch()
+    assert {rec[200] for rec in records} == set(range(166))  # the seeds' pos: exactly every position
+    assert len({rec[201] for rec in records}) > 100          # ... and pos_begin moves with it
+    n = len(records)
+    st, bases, scalars, status, where = K.host_sides(proof * n, records, list(range(n)), [pi] * n)
+    assert st == 0 and status == bytes(n) and where == bytes(n)
+    for i, lab in enumerate(K.SEED_LABELS):
+        assert K.grouped(bases, scalars, i, ROWS * n) == K.model_grouped(K.model_sides(proof, vk, pi, lab)), len(lab)
+
+
+def test_the_smallest_and_largest_keys_with_long_public_inputs():
+    """n = 1 and n = 2^32 (log2 n = 0 and 32, the ends of what the routine accepts) and public inputs of 0, 1, 64 and 257 rows: the
+    batch tests/test_gpu_plonk_sides.py compares the device with the host on, here the host against verifier.sides"""
+    data, records, index, pis, keyed = K.extreme_batch()
+    assert sorted(rec[203] for rec in records) == [0, 12, 32]  # log2_n
+    n = len(index)
+    st, bases, scalars, status, where = K.host_sides(data, records, index, pis)
+    assert st == 0 and status == bytes(n) and where == bytes(n)
+    for i in range(n):
+        vk, lab = keyed[index[i]]
+        want = K.model_sides(data[K.PROOF * i:K.PROOF * (i + 1)], vk, pis[i], lab)
+        assert K.grouped(bases, scalars, i, ROWS * n) == K.model_grouped(want), (i, vk.n, len(pis[i] or {}))
 
 
 def test_a_batch_with_mixed_keys_ragged_inputs_and_a_wider_stride(keys, proofs):
