@@ -239,6 +239,12 @@ inline void max_bound_ragged(StandardComposer &c, const pg_scalar *d_max_range, 
                              pg_variable *d_result_vars, uint32_t *d_num_bits) {
     pg_throw(pg_composer_max_bound_ragged_batch(c.h, d_max_range, d_witness, batch, d_result_vars, d_num_bits), "Batched::max_bound_ragged");
 }
+// one public (min, max) pair per item
+inline void range_check_ragged(StandardComposer &c, const pg_scalar *d_min_range, const pg_scalar *d_max_range, const pg_scalar *d_witness,
+                               uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits) {
+    pg_throw(pg_composer_range_check_ragged_batch(c.h, d_min_range, d_max_range, d_witness, batch, d_result_vars, d_num_bits),
+             "Batched::range_check_ragged");
+}
 inline void scalar_decomposition(StandardComposer &c, uint64_t num_bits, const pg_variable *d_witness_var, const pg_scalar *d_witness,
                                  uint64_t batch, pg_variable *d_result_vars) {
     pg_throw(pg_composer_scalar_decomposition_batch(c.h, num_bits, d_witness_var, d_witness, batch, d_result_vars),

@@ -216,12 +216,32 @@ pg_status pg_max_bound_ragged_batch(pg_engine *e, const pg_scalar *d_max_range, 
                                     const uint64_t *d_var_off, uint64_t gate_base, uint64_t var_base,
                                     const pg_columns *out, pg_variable *d_result_vars /* may be NULL */, void *stream);
 
+/* Ragged range_check: one public (min, max) pair PER ITEM (two device arrays).  For every item i,
+ *     w = AllocatedScalar::allocate(composer, witness[i]);
+ *     result[i] = range_check(composer, min[i], max[i], w);               src/range.rs:27-43
+ * The ladder length n_i comes from max[i] alone (min_bound reuses it, :34-37): 4 n_i + 11 rows and 2 n_i + 524 variables per
+ * item, at most 1031 and 1034.  The plan is pg_max_bound_ragged_plan's with these weights (same buffers, same totals, it
+ * synchronises `stream`); the batch call emits at its offsets, the values call writes the assignments alone (a witness refresh
+ * under the plan of the same bounds). */
+pg_status pg_range_check_ragged_plan(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                     uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream);
+pg_status pg_range_check_ragged_batch(pg_engine *e, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                      const pg_scalar *d_witness, uint64_t batch, const uint32_t *d_num_bits,
+                                      const uint64_t *d_row_off, const uint64_t *d_var_off, uint64_t gate_base, uint64_t var_base,
+                                      const pg_columns *out, pg_variable *d_result_vars /* may be NULL */, void *stream);
+pg_status pg_range_check_ragged_values_batch(pg_engine *e, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                             const pg_scalar *d_witness, uint64_t batch, const uint32_t *d_num_bits,
+                                             const uint64_t *d_row_off, const uint64_t *d_var_off, pg_scalar *d_var_values,
+                                             void *stream);
+
 /* Asynchronous plans: enqueue and return at once; the totals (and the error count) land in engine-owned pinned host
  * memory and are read with pg_plan_result once the stream has been synchronised.  For callers that pre-allocate
- * worst-case buffers (10 rows / 15 variables per mix item, 515 rows / 517 variables per max_bound item) and do not
+ * worst-case buffers (10 rows / 15 variables per mix item, 515 rows / 517 variables per max_bound item, 1031 / 1034 per range_check item) and do not
  * want a host round trip between the plan and the emit call. */
 pg_status pg_max_bound_ragged_plan_async(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
                                          uint64_t *d_row_off, uint64_t *d_var_off, void *stream);
+pg_status pg_range_check_ragged_plan_async(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                           uint64_t *d_row_off, uint64_t *d_var_off, void *stream);
 pg_status pg_scalar_mix_plan_async(pg_engine *e, const pg_scalar *d_v, uint64_t batch, uint64_t *d_row_off,
                                    uint64_t *d_var_off, uint8_t *d_err_mask /* may be NULL */, void *stream);
 /* totals of the engine's most recent plan; PG_ERR_NON_EXISTING_INVERSE when that plan found failing items */
@@ -451,6 +471,9 @@ pg_status pg_composer_boolean_gate_batch(pg_composer *c, const pg_variable *d_a,
  * per-item offsets for the permutation, and emits.
  *   max_bound_ragged: for i { allocate(d_witness[i]); max_bound(composer, d_max_range[i], w) } -- one public bound per
  *                     item; d_num_bits_out (device u32[batch], may be NULL) receives the u64 each call returns
+ *   range_check_ragged: for i { allocate(d_witness[i]); range_check(composer, d_min_range[i], d_max_range[i], w) } -- one
+ *                     public interval per item; d_num_bits_out as above.  After pg_composer_clear_witness the same call with
+ *                     the same two bound arrays is found in place and only its assignments are written
  *   is_non_zero:      for i { is_non_zero(composer, d_var[i], value of d_var[i]) }; an item whose value is 0 stops after
  *                     its first variable + row (src/scalar.rs:69-79); returns PG_ERR_NON_EXISTING_INVERSE when any did
  *                     (everything is appended all the same, like a loop that records the error and carries on);
@@ -458,6 +481,9 @@ pg_status pg_composer_boolean_gate_batch(pg_composer *c, const pg_variable *d_a,
  *   scalar_mix:       the fused item of pg_scalar_mix_batch (BASELINE config 3) */
 pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_max_range, const pg_scalar *d_witness,
                                              uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out);
+pg_status pg_composer_range_check_ragged_batch(pg_composer *c, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                               const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars,
+                                               uint32_t *d_num_bits_out);
 pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask,
                                         uint64_t *err_count);
 pg_status pg_composer_scalar_mix_batch(pg_composer *c, const pg_scalar *d_v, const pg_scalar *d_y, const pg_scalar *d_s,

@@ -121,6 +121,14 @@ SIGNATURES = {
                                            _P(LayoutC), C.c_void_p]),
     "pg_max_bound_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
                                             C.c_void_p, C.c_uint64, C.c_uint64, _P(ColumnsC), C.c_void_p, C.c_void_p]),
+    "pg_range_check_ragged_plan": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                             _P(LayoutC), C.c_void_p]),
+    "pg_range_check_ragged_plan_async": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                   C.c_void_p]),
+    "pg_range_check_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, C.c_uint64, C.c_uint64, _P(ColumnsC), C.c_void_p, C.c_void_p]),
+    "pg_range_check_ragged_values_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_conditionally_select_zero_batch": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64] * 3 + [_P(ColumnsC), C.c_void_p,
                                                                                             C.c_void_p]),
     "pg_conditionally_select_one_batch": (C.c_int, [C.c_void_p] * 5 + [C.c_uint64] * 3 + [_P(ColumnsC), C.c_void_p,
@@ -183,6 +191,8 @@ SIGNATURES = {
     "pg_composer_conditionally_select_one_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_composer_maybe_equal_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_composer_max_bound_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_composer_range_check_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
+                                                       C.c_void_p]),
     "pg_composer_is_non_zero_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, _P(C.c_uint64)]),
     "pg_composer_scalar_mix_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64,
                                                C.c_void_p, C.c_void_p, _P(C.c_uint64)]),

@@ -249,6 +249,20 @@ class StandardComposer:
                                                           res.data_ptr(), nb.data_ptr()), "pg_composer_max_bound_ragged_batch")
         return res, nb
 
+    def range_check_ragged_batch(self, min_range: torch.Tensor, max_range: torch.Tensor, witness: torch.Tensor):
+        """for i: allocate(witness[i]); range_check(min_range[i], max_range[i], w) -> (result Variables, num_bits per item)"""
+        for x in (min_range, max_range, witness):
+            assert x.is_cuda and x.dtype == torch.int64 and x.dim() == 2 and x.shape[1] == 4 and x.is_contiguous()
+        if not (min_range.shape[0] == max_range.shape[0] == witness.shape[0]):
+            raise ValueError(f"min_range, max_range and witness differ in length: {min_range.shape[0]}, {max_range.shape[0]}, "
+                             f"{witness.shape[0]}")
+        res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
+        nb = torch.empty((witness.shape[0],), dtype=torch.int32, device=witness.device)
+        _chk(self._lib.pg_composer_range_check_ragged_batch(self._h, min_range.data_ptr(), max_range.data_ptr(), witness.data_ptr(),
+                                                            witness.shape[0], res.data_ptr(), nb.data_ptr()),
+             "pg_composer_range_check_ragged_batch")
+        return res, nb
+
     def is_non_zero_batch(self, vars_: torch.Tensor):
         """for i: is_non_zero(vars[i], its value) -> (error mask, error count); items whose value is 0 stop early and are
         reported here instead of raising (the reference returns Err(NonExistingInverse) for them)"""

@@ -133,7 +133,8 @@ pg_status ensure_scratch(pg_engine *e, uint64_t batch) {
 
 // what a plan kernel is handed to finish the prefix sums itself (up to kPlanFusedBlocks blocks; beyond, fused = 0 and
 // scan_counts launches the two-level scan)
-pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_t *d_var_off, bool with_errs) {
+pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_t *d_var_off, bool with_errs,
+                       uint32_t fused_blocks = pg::kPlanFusedBlocks) {
     const uint64_t nblk = (batch + pg::kScanBlock - 1) / pg::kScanBlock;
     pg::PlanScan P{};
     P.agg = e->d_blk_agg.as<unsigned long long>();
@@ -147,7 +148,7 @@ pg::PlanScan plan_scan(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64
 #if defined(PG_PLAN_TWO_LAUNCHES)  // A/B build
     P.fused = 0;
 #else
-    P.fused = nblk <= pg::kPlanFusedBlocks ? 1u : 0u;
+    P.fused = nblk <= fused_blocks ? 1u : 0u;
 #endif
     return P;
 }
@@ -165,9 +166,9 @@ pg_status plan_totals(pg_engine *e, uint64_t *n_rows, uint64_t *n_vars) {
 // counts in e->d_rows / e->d_vars and their block sums in e->d_blk_* (both left by the plan kernel) -> exclusive prefix
 // sums; totals copied back (the synchronous form synchronises the stream).  Nothing to launch after a fused plan.
 pg_status scan_counts(pg_engine *e, uint64_t batch, uint64_t *d_row_off, uint64_t *d_var_off, uint64_t *n_rows,
-                      uint64_t *n_vars, hipStream_t st, bool with_errs) {
+                      uint64_t *n_vars, hipStream_t st, bool with_errs, uint32_t fused_blocks = pg::kPlanFusedBlocks) {
     const uint32_t nblk = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
-    if (!plan_scan(e, batch, d_row_off, d_var_off, with_errs).fused) {
+    if (!plan_scan(e, batch, d_row_off, d_var_off, with_errs, fused_blocks).fused) {
         const uint32_t prefixed = nblk > pg::kScanDirectBlocks ? 1u : 0u;
         if (prefixed)
             hipLaunchKernelGGL(pg::scan_top_kernel, dim3(1), dim3(pg::kThreads), 0, st, e->d_blk_rows.as<uint64_t>(),
@@ -784,8 +785,16 @@ pg_status pg_max_bound_allocated_batch(pg_engine *e, const pg_scalar *max_range,
     return max_bound_common(e, max_range, d_witness_var, d_witness, batch, gate_base, var_base, out, d_result_vars, stream);
 }
 
-static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
-                                              uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream) {
+}  // extern "C"
+
+// the plan of a batch with one upper bound per item; KIND: what an item weighs (max_bound, or range_check: two blocks on max's ladder length)
+template <uint32_t KIND>
+static pg_status bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                          uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream) {
+    // (a fused plan's published prefixes hold 31 bits of rows and of variables, emit.hpp: blocks x 1024 items x the largest item --
+    // 2048 blocks for max_bound's 517, 2028 for range_check's 1034)
+    constexpr uint64_t kLargest = std::max(pg::kind_rows(KIND, 255), pg::kind_vars(KIND, 255));
+    constexpr uint32_t kFused = (uint32_t)std::min<uint64_t>(pg::kPlanFusedBlocks, ((1ull << 31) - 1) / (pg::kScanBlock * kLargest));
     if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (out) std::memset(out, 0, sizeof *out);
     if (batch == 0) {
@@ -803,15 +812,21 @@ static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_m
     PG_TRY(enter_stream(e, st));
     StreamScope scope{e, st};
     const uint32_t grid = (uint32_t)((batch + pg::kScanBlock - 1) / pg::kScanBlock);
-    hipLaunchKernelGGL(pg::max_bound_plan_kernel, dim3(grid), dim3(pg::kThreads), 0, st,
+    hipLaunchKernelGGL(pg::max_bound_plan_kernel<KIND>, dim3(grid), dim3(pg::kThreads), 0, st,
                        reinterpret_cast<const uint4 *>(d_max_range), batch, e->d_pow2.as<uint4>(), d_num_bits, e->d_rows.as<uint32_t>(),
-                       e->d_vars.as<uint32_t>(), plan_scan(e, batch, d_row_off, d_var_off, false));
+                       e->d_vars.as<uint32_t>(), plan_scan(e, batch, d_row_off, d_var_off, false, kFused));
     PG_HIP_TRY(hipGetLastError());
     // a max_bound plan has no failing items: the scan writes errs = 0 with the totals, in stream order
-    if (!out) return scan_counts(e, batch, d_row_off, d_var_off, nullptr, nullptr, st, false);
-    PG_TRY(scan_counts(e, batch, d_row_off, d_var_off, &out->n_gates, &out->n_vars, st, false));
+    if (!out) return scan_counts(e, batch, d_row_off, d_var_off, nullptr, nullptr, st, false, kFused);
+    PG_TRY(scan_counts(e, batch, d_row_off, d_var_off, &out->n_gates, &out->n_vars, st, false, kFused));
     return PG_OK;
 }
+static pg_status max_bound_ragged_plan_common(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                              uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream) {
+    return bound_ragged_plan_common<pg::WIRES_MAX_BOUND>(e, d_max_range, batch, d_num_bits, d_row_off, d_var_off, out, stream);
+}
+
+extern "C" {
 
 pg_status pg_max_bound_ragged_plan(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
                                    uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream) {
@@ -868,6 +883,59 @@ pg_status pg_max_bound_ragged_values_batch(pg_engine *e, const pg_scalar *d_max_
                                            pg_scalar *d_var_values, void *stream) {
     const pg_columns c = values_columns(d_var_values);
     return max_bound_ragged_common(e, d_max_range, d_witness, batch, d_num_bits, d_row_off, d_var_off, 0, 0, &c, nullptr, stream, true);
+}
+
+/* ---- range_check, one (min, max) pair per item ------------------------------ */
+pg_status pg_range_check_ragged_plan(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                     uint64_t *d_row_off, uint64_t *d_var_off, pg_layout *out, void *stream) {
+    if (!out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    return bound_ragged_plan_common<pg::WIRES_RANGE_CHECK>(e, d_max_range, batch, d_num_bits, d_row_off, d_var_off, out, stream);
+}
+
+pg_status pg_range_check_ragged_plan_async(pg_engine *e, const pg_scalar *d_max_range, uint64_t batch, uint32_t *d_num_bits,
+                                           uint64_t *d_row_off, uint64_t *d_var_off, void *stream) {
+    return bound_ragged_plan_common<pg::WIRES_RANGE_CHECK>(e, d_max_range, batch, d_num_bits, d_row_off, d_var_off, nullptr, stream);
+}
+
+static pg_status range_check_ragged_common(pg_engine *e, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                           const pg_scalar *d_witness, uint64_t batch, const uint32_t *d_num_bits,
+                                           const uint64_t *d_row_off, const uint64_t *d_var_off, uint64_t gate_base, uint64_t var_base,
+                                           const pg_columns *out, pg_variable *d_result_vars, void *stream, bool values_only) {
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "engine is NULL");
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_scalars(d_min_range, "d_min_range"));
+    PG_TRY(check_scalars(d_max_range, "d_max_range"));
+    PG_TRY(check_scalars(d_witness, "d_witness"));
+    if (!d_num_bits) return fail(PG_ERR_INVALID_ARGUMENT, "d_num_bits is NULL");
+    PG_TRY(check_u64s(d_row_off, "d_row_off"));
+    PG_TRY(check_u64s(d_var_off, "d_var_off"));
+    PG_TRY(check_u64s(d_result_vars, "d_result_vars", true));
+    PG_TRY(check_columns(out));
+    pg::RangeBoundsGD::Args A{};
+    A.min_range_v = reinterpret_cast<const uint4 *>(d_min_range);
+    A.max_range_v = reinterpret_cast<const uint4 *>(d_max_range);
+    A.num_bits_v = d_num_bits;
+    A.witness = reinterpret_cast<const uint4 *>(d_witness);
+    A.result_vars = d_result_vars;
+    A.pow2 = e->d_pow2.as<uint4>();
+    return launch<pg::RangeBoundsGD>(e, A, out, batch, gate_base, var_base, 0, d_row_off, d_var_off, stream, nullptr, values_only);
+}
+
+pg_status pg_range_check_ragged_batch(pg_engine *e, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                      const pg_scalar *d_witness, uint64_t batch, const uint32_t *d_num_bits,
+                                      const uint64_t *d_row_off, const uint64_t *d_var_off, uint64_t gate_base, uint64_t var_base,
+                                      const pg_columns *out, pg_variable *d_result_vars, void *stream) {
+    return range_check_ragged_common(e, d_min_range, d_max_range, d_witness, batch, d_num_bits, d_row_off, d_var_off, gate_base, var_base,
+                                     out, d_result_vars, stream, false);
+}
+
+pg_status pg_range_check_ragged_values_batch(pg_engine *e, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                             const pg_scalar *d_witness, uint64_t batch, const uint32_t *d_num_bits,
+                                             const uint64_t *d_row_off, const uint64_t *d_var_off, pg_scalar *d_var_values,
+                                             void *stream) {
+    const pg_columns c = values_columns(d_var_values);
+    return range_check_ragged_common(e, d_min_range, d_max_range, d_witness, batch, d_num_bits, d_row_off, d_var_off, 0, 0, &c, nullptr,
+                                     stream, true);
 }
 
 /* ---- scalar gadgets ------------------------------------------------------- */

@@ -208,8 +208,9 @@ pg_status check_var_arrays(pg_composer *c, std::initializer_list<const pg_variab
     if (digest) *digest = pg_composer::Sig{c->totals()[1], c->totals()[2]};
     return PG_OK;
 }
-// the same digest of a device array of scalars (per-item public bounds): n * 4 words
-pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_composer::Sig *digest) {
+// the same digest of a device array of scalars (per-item public bounds): n * 4 words; d2 (may be NULL): a second such array, salted
+// by its place like check_var_arrays' (the two arrays swapped digest differently)
+pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_composer::Sig *digest, const pg_scalar *d2 = nullptr) {
     *digest = pg_composer::Sig{0, 0};
     if (n == 0) return PG_OK;
     PG_HIP_TRY(hipSetDevice(c->e->device));
@@ -218,6 +219,9 @@ pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_comp
     const uint64_t words = 4 * n, want = (words + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
     hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream,
                        reinterpret_cast<const uint64_t *>(d), words, d_out, 0x13198a2e03707344ull);
+    if (d2)
+        hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream,
+                           reinterpret_cast<const uint64_t *>(d2), words, d_out, 0x13198a2e03707344ull + 0x9e3779b97f4a7c15ull);
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -322,11 +326,16 @@ pg_status flush_gates(pg_composer *c, size_t i, size_t j) {
 // launch: the same rows as the batched append of that gadget (a circuit built the reference's way, one allocate + range_check at a
 // time: sigma of 17 M rows 3.5 -> 0.3 ms), but short runs stay what they were (rows of single calls): a footprint per run of two
 // calls would be a launch per run in sigma.
+// the ladder kinds whose batched append takes its public bounds per item (ragged_batch: the footprint keeps the call's prefix sums)
+constexpr bool per_item_bounds_kind(uint32_t wire_kind) { return wire_kind == pg::WIRES_MAX_BOUND || wire_kind == pg::WIRES_RANGE_CHECK; }
+
 void add_footprint(pg_composer *c, const pg::PermSeg &f, bool only_if_long = false) {
     if (!f.items) return;
     // what lets perm_route's questions be asked in any order (footprint.hpp)
     assert(!pg::is_template_kind(f.wire_kind) || f.wire_n == 0);
-    assert(!f.row_off || f.wire_kind == pg::WIRES_UNKNOWN || pg::is_template_kind(f.wire_kind) || (f.wire_kind == pg::WIRES_MAX_BOUND && f.tail == 0));
+    // (the ladder kinds with a bound -- or a pair of bounds -- per item: never with a tail, never with a ladder length of the call's)
+    assert(!f.row_off || f.wire_kind == pg::WIRES_UNKNOWN || pg::is_template_kind(f.wire_kind) ||
+           (per_item_bounds_kind(f.wire_kind) && f.tail == 0 && f.wire_n == 0));
     pg::PermSeg *last = c->segs.empty() ? nullptr : &c->segs.back();
     if (last && !last->row_off && !f.row_off && last->gate_end == f.gate_base && last->var_end == f.var_base && last->L == f.L && last->V == f.V &&
         last->wire_kind == f.wire_kind && last->wire_n == f.wire_n && last->tail == f.tail) {
@@ -1143,7 +1152,7 @@ namespace {
 // A batch without failing items of a kind whose full items are all alike leaves a uniform footprint.
 template <class Plan, class Sign, class Emit>
 pg_status ragged_batch(pg_composer *c, uint32_t wire_kind, uint64_t batch, uint64_t *err_count, Plan plan, Sign sign, Emit emit) {
-    const bool per_item_bounds = wire_kind == pg::WIRES_MAX_BOUND;
+    const bool per_item_bounds = per_item_bounds_kind(wire_kind);
     RaggedBuffers b;
     PG_TRY(ragged_alloc(batch, per_item_bounds, &b));
     pg_layout lay;
@@ -1207,6 +1216,34 @@ pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
             PG_TRY(max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at, d_result_vars,
                                            c->stream, in_place));
+            if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits.get(), batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
+                return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
+            return PG_OK;
+        });
+}
+
+pg_status pg_composer_range_check_ragged_batch(pg_composer *c, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                               const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars,
+                                               uint32_t *d_num_bits_out) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(flush(c));
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_scalars(d_min_range, "d_min_range"));  // (digested before the engine call that checks the others)
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    return ragged_batch(
+        c, pg::WIRES_RANGE_CHECK, batch, nullptr,
+        [&](RaggedBuffers &b, pg_layout *lay, uint64_t *) {
+            return pg_range_check_ragged_plan(c->e, d_max_range, batch, b.bits(), b.rows(), b.vars(), lay, c->stream);
+        },
+        [&](uint64_t, pg_composer::Sig *sig) {  // the rows: both arrays of per-item public bounds and where the call lands
+            pg_composer::Sig dg;
+            PG_TRY(digest_scalars(c, d_max_range, batch, &dg, d_min_range));
+            *sig = gadget_sig(c, 30, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
+            return PG_OK;
+        },
+        [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
+            PG_TRY(range_check_ragged_common(c->e, d_min_range, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at,
+                                             d_result_vars, c->stream, in_place));
             if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits.get(), batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
                 return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
             return PG_OK;

@@ -133,8 +133,9 @@ enum PermRoute : uint32_t {
     PERM_TEMPLATE_RAGGED,  // perm_template_kernel<true>: the same with items that stopped at is_non_zero's error
 };
 // The questions are asked in this order (it decides where more than one could say yes; no footprint that is created does that:
-// template kinds have wire_n == 0, and of the ladder kinds only WIRES_MAX_BOUND is ever ragged, never with a tail -- capi_composer.inc,
-// add_footprint, asserts both).
+// template kinds have wire_n == 0, and of the ladder kinds only WIRES_MAX_BOUND and WIRES_RANGE_CHECK are ever ragged -- a bound, or a
+// (min, max) pair, per item -- never with a tail -- capi_composer.inc, add_footprint, asserts both.  Ragged WIRES_RANGE_CHECK has no closed
+// form yet: it answers no question and falls to PERM_ITEMS, and to the windowed MAT_READ_WIRES below).
 inline PermRoute perm_route(const PermSeg &s) {
     if (s.wire_kind != WIRES_UNKNOWN && !s.row_off && s.wire_n >= 2) return PERM_LADDER;
     if (is_template_kind(s.wire_kind) && s.tail == 0) return s.row_off ? PERM_TEMPLATE_RAGGED : PERM_TEMPLATE;

@@ -23,6 +23,7 @@
 #pragma once
 
 #include "emit.hpp"
+#include "footprint.hpp"
 #include "invert.hpp"
 
 namespace pg {
@@ -260,6 +261,132 @@ struct RangeCheckGD {
     __device__ static uint32_t region_k(const Args &A, const ItemRec &, uint32_t b, uint32_t kk) { return xo(A) + b * (A.n + 261) + kk; }
 };
 
+// ---- range_check with one public (min, max) pair PER ITEM -----------------------------------------------------------------
+// The same item as RangeCheckGD's with the witness allocated by the item ([x | max block | min block | R], 4 n_i + 11 rows and
+// 2 n_i + 524 variables), but the ladder length n_i (from max_i alone: min_bound reuses it, range.rs:34-37) and the two selector
+// constants q_c = mont(max_i - 1), mont(-min_i) differ from item to item: all three are functions of the PUBLIC bounds, so they are
+// item_rows' part of the record and the rows of the call never read a witness.  A type of its own: RangeCheckGD's uniform paths
+// stay what they are.
+struct RangeBoundsGD {
+    struct Args {
+        const uint4 *min_range_v, *max_range_v;  // per-item bounds (Montgomery form)
+        const uint32_t *num_bits_v;              // per-item ladder bits (from the plan)
+        const uint4 *witness;
+        uint64_t *result_vars;
+        const uint4 *pow2;
+    };
+    static constexpr int kInv = 2;
+    static constexpr bool kInvDense = true;
+    static constexpr int kInvGroup = 4;
+    // element e of item: u of the max block (e = 0) / min block (e = 1) -- the witness, that block's bound and the ladder length
+    __device__ static void inv_operands(const Args &A, const EmitOut &, uint64_t item, uint32_t e, FrVec &p, FrVec &q, uint32_t &n) {
+        const uint4 *bound = e == 0 ? A.max_range_v : A.min_range_v;  // (a select of two pointers: no branch)
+        p.v[0] = A.witness[item * 2];
+        p.v[1] = A.witness[item * 2 + 1];
+        q.v[0] = bound[item * 2];
+        q.v[1] = bound[item * 2 + 1];
+        n = A.num_bits_v[item];
+    }
+    __device__ static Fr inv_combine(const Args &, uint32_t e, const Fr &x, const Fr &m, uint32_t n) {
+        // both flavours of T from the one bound the element was given, the wanted one selected limb by limb (RangeCheckGD)
+        const Fr t0 = fr_sub(fr_sub(m, fr_one()), x), t1 = fr_sub(x, m);
+        Fr Tm;
+#pragma unroll
+        for (int i = 0; i < 4; i++) Tm.l[i] = e == 0 ? t0.l[i] : t1.l[i];
+        return bound_u(Tm, fr_from_mont(Tm), n);
+    }
+    __device__ static uint4 *inv_slot(const Args &A, const EmitOut &O, uint64_t item, uint32_t e) {
+        const uint32_t n = A.num_bits_v[item];
+        return O.vars + 2 * (O.var_off[item] + 1 + e * (n + 261) + bound_z_offset(n));
+    }
+    struct alignas(16) ItemRec {
+        Fr x;
+        Fr qc[2];  // mont(max - 1), mont(-min) of this item: row 0 of its max / min block
+        BoundRec b[2];
+        uint32_t y[2];
+        uint32_t n, pad;
+    };
+    static constexpr int W = PG_RC_W;
+    static constexpr bool kRagged = true, kRecInRows = true, kUsePow2 = true;
+    static constexpr uint32_t kUniformRows = 0, kUniformVars = 0;  // ladder lengths differ from item to item
+
+    __device__ static const uint4 *pow2(const Args &A) { return A.pow2; }
+    __device__ static void fill_table(const Args &, uint4 *table, uint32_t tid) {
+        if (tid == T_QC_A || tid == T_QC_B) {  // (the items' own, from their records)
+            table[2 * tid] = make_uint4(0, 0, 0, 0);
+            table[2 * tid + 1] = make_uint4(0, 0, 0, 0);
+        }
+    }
+    __device__ static void item_rows(const Args &A, const EmitOut &, uint64_t item, const uint4 *, ItemRec &R) {
+        FrVec mx, mn;
+        mx.v[0] = A.max_range_v[item * 2];
+        mx.v[1] = A.max_range_v[item * 2 + 1];
+        mn.v[0] = A.min_range_v[item * 2];
+        mn.v[1] = A.min_range_v[item * 2 + 1];
+        R.qc[0] = fr_sub(mx.f, fr_one());  // range.rs:87
+        R.qc[1] = fr_neg(mn.f);            // range.rs:63
+        R.n = A.num_bits_v[item];
+    }
+    __device__ static void item(const Args &A, const EmitOut &O, uint64_t item, const uint4 *, ItemRec &R) {
+        FrVec x;
+        x.v[0] = A.witness[item * 2];
+        x.v[1] = A.witness[item * 2 + 1];
+        R.x = x.f;
+        const uint32_t n = R.n;  // (item_rows', like qc: read, never rewritten)
+        bound_fetch_z(O, item, R.b[0]);
+        bound_fetch_z(O, O.batch + item, R.b[1]);
+        R.y[0] = bound_item(fr_sub(R.qc[0], x.f), n, R.b[0]);  // T = (max-1) - x, range.rs:102
+        R.y[1] = bound_item(fr_add(x.f, R.qc[1]), n, R.b[1]);  // T = x - min, range.rs:69
+        if (A.result_vars) A.result_vars[item] = O.var_base + O.var_off[item] + (2 * n + 523);  // R is the item's last variable
+    }
+    __device__ static void selectors(const Args &, const ItemRec &R, uint32_t j, const uint4 *table, uint32_t h, uint4 out[5]) {
+        const uint32_t L = 2 * R.n + 5;
+        uint32_t id[5];
+        if (j == 2 * L) {  // y1 * y2, range.rs:42
+            id[0] = T_ONE; id[1] = T_ZERO; id[2] = T_ZERO; id[3] = T_NEG1; id[4] = T_ZERO;
+        } else {
+            const bool is_min = j >= L;
+            bound_selector_ids(is_min ? j - L : j, R.n, is_min, id);
+        }
+        ids_to_values(id, table, h, out);
+        // the only data-dependent selectors: q_c of the two bound add rows (the wanted 16-byte half straight from the record)
+        if (id[4] == T_QC_A || id[4] == T_QC_B) out[4] = reinterpret_cast<const uint4 *>(R.qc)[2 * (id[4] - T_QC_A) + h];
+    }
+    __device__ static void wires(const Args &, const EmitOut &, const ItemRec &R, uint64_t, uint64_t vbase, uint32_t j, uint64_t out[3]) {
+        const uint32_t n = R.n, L = 2 * n + 5, VB = n + 261;
+        uint32_t off[3];
+        if (j == 2 * L) {
+            off[0] = 1 + 260 + n;       // Y1
+            off[1] = 1 + VB + 260 + n;  // Y2
+            off[2] = 1 + 2 * VB;        // R
+        } else {
+            const bool is_min = j >= L;
+            bound_wire_offsets(is_min ? j - L : j, n, is_min ? 1 + VB : 1, kWitnessWire, off);
+        }
+#pragma unroll
+        for (int c = 0; c < 3; c++) out[c] = off[c] == kWitnessWire ? vbase : vbase + off[c];
+    }
+    __device__ static bool is_inv_slot(const Args &, const ItemRec &R, uint32_t k) {
+        const uint32_t VB = R.n + 261, z = bound_z_offset(R.n);
+        return k == 1 + z || k == 1 + VB + z;
+    }
+    __device__ static Fr var_value(const Args &, const ItemRec &R, const uint4 *, uint32_t k) {
+        const uint32_t n = R.n, VB = n + 261;
+        if (k == 0) return R.x;
+        k -= 1;
+        if (k == 2 * VB) return (R.y[0] & R.y[1]) ? fr_one() : fr_zero();  // range.rs:42
+        uint32_t kk = k, blk = 0;
+        if (kk >= VB) { kk -= VB; blk = 1; }
+        return bound_var_value(R.b[blk], R.y[blk], kk, n);
+    }
+    // the region sweep of a witness refresh (emit.hpp): two blocks per item, where they lie decided by the item's own ladder length
+    static constexpr bool kRegionVars = true;
+    static constexpr uint32_t kBlocks = 2;
+    __device__ static uint32_t region_n(const Args &, const ItemRec &R) { return R.n; }
+    __device__ static const BoundRec &region_block(const ItemRec &R, uint32_t b) { return R.b[b]; }
+    __device__ static uint32_t region_k(const Args &, const ItemRec &R, uint32_t b, uint32_t kk) { return 1 + b * (R.n + 261) + kk; }
+};
+
 // ---- max_bound: one public bound for the whole batch, or one bound per item ----
 template <bool RAGGED>
 struct MaxBoundGD {
@@ -478,9 +605,12 @@ struct DecompositionGD {
     // (num_bits may be 256 here, range.rs:134: 257 accumulators, one more than a wave-pass of four per lane holds -- the last goes with U z y)
 };
 
-// plan of a ragged max_bound batch: ladder bits and row/variable counts per item (range.rs:87-90)
+// plan of a batch with one upper bound per item: ladder bits and row/variable counts per item (range.rs:87-90).  KIND: what an item
+// weighs (footprint.hpp) -- WIRES_MAX_BOUND, or WIRES_RANGE_CHECK, whose min block reuses the ladder length of max (range.rs:34-37)
+template <uint32_t KIND>
 __global__ __launch_bounds__(kThreads) void max_bound_plan_kernel(const uint4 *max_range, uint64_t batch, const uint4 *pow2,
                                                                  uint32_t *num_bits, uint32_t *rows, uint32_t *vars, const PlanScan P) {
+    constexpr uint32_t kR0 = kind_rows(KIND), kR1 = kind_rows(KIND, 1) - kR0, kV0 = kind_vars(KIND), kV1 = kind_vars(KIND, 1) - kV0;
     uint32_t r[4] = {0, 0, 0, 0}, v[4] = {0, 0, 0, 0};
 #pragma unroll
     for (int k = 0; k < 4; k++) {
@@ -498,8 +628,8 @@ __global__ __launch_bounds__(kThreads) void max_bound_plan_kernel(const uint4 *m
             uint32_t n = raw_bit_length(fr_from_mont(p.f));
             if (n < 1) n = 1;
             num_bits[i] = n;
-            r[k] = 2 * n + 5;
-            v[k] = n + 262;
+            r[k] = kR0 + kR1 * n;
+            v[k] = kV0 + kV1 * n;
         }
     }
     plan_store(P, r, v, batch, rows, vars);  // the prefix sums, same launch

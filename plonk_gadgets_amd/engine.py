@@ -302,6 +302,28 @@ class Engine:
             raise PgError(st, "pg_max_bound_ragged_batch")
         return out, res, nb, lay
 
+    # ---- range_check, one (min, max) pair per item ---------------------------------
+    def _check_bound_arrays(self, min_range: torch.Tensor, max_range: torch.Tensor, witness: torch.Tensor) -> int:
+        for t in (min_range, max_range, witness):
+            self._check_scalars(t)
+        if not (min_range.shape[0] == max_range.shape[0] == witness.shape[0]):
+            raise ValueError(f"min_range, max_range and witness differ in length: {min_range.shape[0]}, {max_range.shape[0]}, "
+                             f"{witness.shape[0]}")
+        return witness.shape[0]
+
+    def range_check_ragged_batch(self, min_range: torch.Tensor, max_range: torch.Tensor, witness: torch.Tensor,
+                                 gate_base: int = 0, var_base: int = 0):
+        """one public (min, max) pair PER ITEM (device tensors): for i { allocate(witness[i]); range_check(min[i], max[i], w) }
+        -- plan (ladder bits from max + prefix sums on the device) then emit.
+        Returns (Columns, result_vars, num_bits[int32 tensor], layout)."""
+        batch = self._check_bound_arrays(min_range, max_range, witness)
+        nb, roff, voff = self.ragged_buffers(batch)
+        lay = self.range_check_ragged_plan(max_range, nb, roff, voff)
+        out = Columns.allocate(lay.n_gates, lay.n_vars, self.device, gate_base, var_base)
+        res = torch.empty((batch,), dtype=torch.int64, device=self.device)
+        self.range_check_ragged_emit(min_range, max_range, witness, nb, roff, voff, out, res, gate_base, var_base)
+        return out, res, nb, lay
+
     # ---- scalar gadgets ----------------------------------------------------------
     def _scalar2(self, fn_name, per_item, a_var, a_val, b_var, b_val, gate_base, var_base, out):
         batch = a_var.shape[0]
@@ -866,6 +888,26 @@ class Engine:
         if st != 0:
             raise PgError(st, "pg_max_bound_ragged_batch")
 
+    def range_check_ragged_plan(self, max_range: torch.Tensor, num_bits, row_off, var_off) -> Layout:
+        """ladder bits and prefix sums of range_check items from their upper bounds (min_bound reuses max's ladder length)"""
+        lay = _lib.LayoutC()
+        st = self._lib.pg_range_check_ragged_plan(self._h, max_range.data_ptr(), max_range.shape[0], num_bits.data_ptr(),
+                                                  row_off.data_ptr(), var_off.data_ptr(), C.byref(lay), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_range_check_ragged_plan")
+        return self._layout(lay)
+
+    def range_check_ragged_emit(self, min_range, max_range, witness, num_bits, row_off, var_off, out: Columns, result_vars=None,
+                                gate_base: int = 0, var_base: int = 0):
+        batch = self._check_bound_arrays(min_range, max_range, witness)
+        cols = out.as_c()
+        st = self._lib.pg_range_check_ragged_batch(self._h, min_range.data_ptr(), max_range.data_ptr(), witness.data_ptr(), batch,
+                                                   num_bits.data_ptr(), row_off.data_ptr(), var_off.data_ptr(), gate_base,
+                                                   var_base, C.byref(cols),
+                                                   result_vars.data_ptr() if result_vars is not None else None, self._stream())
+        if st != 0:
+            raise PgError(st, "pg_range_check_ragged_batch")
+
     def scalar_mix_plan(self, v: torch.Tensor, row_off, var_off, err_mask=None):
         """-> (Layout, err_count); PG_ERR_NON_EXISTING_INVERSE is reported through err_count, not raised"""
         lay, nerr = _lib.LayoutC(), C.c_uint64()
@@ -938,6 +980,16 @@ class Engine:
             raise PgError(st, "pg_max_bound_ragged_values_batch")
         return var_values
 
+    def range_check_ragged_values(self, min_range, max_range, witness, num_bits, row_off, var_off, var_values: torch.Tensor):
+        """the ragged range_check's assignments under the plan of its (public) bounds"""
+        batch = self._check_bound_arrays(min_range, max_range, witness)
+        st = self._lib.pg_range_check_ragged_values_batch(self._h, min_range.data_ptr(), max_range.data_ptr(), witness.data_ptr(),
+                                                          batch, num_bits.data_ptr(), row_off.data_ptr(), var_off.data_ptr(),
+                                                          var_values.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_range_check_ragged_values_batch")
+        return var_values
+
     def scalar_mix_values(self, v, y, s, a, b, row_off, var_off, var_values: torch.Tensor, err_mask=None):
         """the fused mix's assignments AND its plan for these witnesses (row_off / var_off / err_mask are outputs; totals:
         plan_result()): an item's shape depends on its witness, the caller compares the plan with the circuit it has"""
@@ -955,6 +1007,12 @@ class Engine:
                                                       row_off.data_ptr(), var_off.data_ptr(), self._stream())
         if st != 0:
             raise PgError(st, "pg_max_bound_ragged_plan_async")
+
+    def range_check_ragged_plan_async(self, max_range: torch.Tensor, num_bits, row_off, var_off):
+        st = self._lib.pg_range_check_ragged_plan_async(self._h, max_range.data_ptr(), max_range.shape[0], num_bits.data_ptr(),
+                                                        row_off.data_ptr(), var_off.data_ptr(), self._stream())
+        if st != 0:
+            raise PgError(st, "pg_range_check_ragged_plan_async")
 
     def scalar_mix_plan_async(self, v: torch.Tensor, row_off, var_off, err_mask=None):
         st = self._lib.pg_scalar_mix_plan_async(self._h, v.data_ptr(), v.shape[0], row_off.data_ptr(), var_off.data_ptr(),
