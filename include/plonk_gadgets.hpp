@@ -261,6 +261,10 @@ inline void conditionally_select_one(StandardComposer &c, const pg_variable *d_y
 inline void maybe_equal(StandardComposer &c, const pg_variable *d_a, const pg_variable *d_b, uint64_t batch, pg_variable *d_result_vars) {
     pg_throw(pg_composer_maybe_equal_batch(c.h, d_a, d_b, batch, d_result_vars), "Batched::maybe_equal");
 }
+// witness < 2^num_bits by the three-wire quad-accumulator widget (num_bits even, 2..254): ceil(num_bits / 6) + 1 rows per item
+inline void range_gate(StandardComposer &c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
+    pg_throw(pg_composer_range_gate_batch(c.h, d_witness_var, num_bits, batch), "Batched::range_gate");
+}
 // Ok, or Error::NonExistingInverse when some item's value was zero (all items are appended either way, the failing
 // ones as far as the reference gets before it returns the error); *err_count = how many
 inline Result is_non_zero(StandardComposer &c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask, uint64_t *err_count) {

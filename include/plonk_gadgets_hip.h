@@ -449,6 +449,19 @@ pg_status pg_composer_conditionally_select_one_batch(pg_composer *c, const pg_va
 pg_status pg_composer_maybe_equal_batch(pg_composer *c, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
                                         pg_variable *d_result_vars);
 
+/* range_gate(witness, num_bits): witness < 2^num_bits by a quad-accumulator widget on the composer's three wires (what the
+ * reference's src/range.rs:11 points its users to for a power-of-two bound; not dusk-plonk's four-wire widget: DESIGN 3.19).
+ * num_bits even, 2 <= num_bits <= 254, else PG_ERR_INVALID_ARGUMENT with nothing appended.  With k = num_bits / 2,
+ * g = ceil(k / 3), pad = 3g - k and v the witness's canonical integer, positions p = 0 .. 3g hold
+ *   P(p) = zero_var (p <= pad);  a new Variable first + (p - pad - 1) of value v >> 2 (3g - p) (pad < p < 3g);  P(3g) = witness
+ * and the item owns g + 1 rows and k - 1 new Variables: row i < g = (P(3i), P(3i+1), P(3i+2)) with q_range = 1, row g =
+ * (witness, zero_var, zero_var) with q_range = 0, all five arithmetic selectors 0.  A row with q_range = 1 states that each
+ * of b - 4a, c - 4b and a_next - 4c lies in {0, 1, 2, 3}.  An out-of-range witness still gets all its rows (its row 0 fails).
+ * On EXISTING Variables, their assignments read from the composer's own table; the batched form checks its array on the
+ * device first.  q_range is written by pg_composer_materialize; pg_composer_check also checks these rows' statements. */
+pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t num_bits);
+pg_status pg_composer_range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch);
+
 /* the composer's gate calls over device arrays of Variables, one set of selectors for the whole batch (no public
  * inputs): the loops
  *   poly_gate:             for i { composer.poly_gate(a[i], b[i], c[i], q_m, q_l, q_r, q_o, q_c, None) }
@@ -612,6 +625,16 @@ pg_status pg_quotient(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p,
 pg_status pg_quotient_blinded(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha,
                               const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4],
                               const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream);
+/* pg_quotient_range: pg_quotient (blinded = 0) or pg_quotient_blinded (blinded != 0) with the range widget's term (DESIGN section
+ * 3.19; pg_composer_range_gate):
+ *   N(x) += q_range(x) [ alpha^3 delta(b - 4a) + alpha^4 delta(c - 4b) + alpha^5 delta(a(omega x) - 4c) ],  delta(f) = f (f-1)(f-2)(f-3)
+ * d_q_range: n coefficients (device, Montgomery form), not blinded; NULL: exactly the launches, and the bytes, of the call it
+ * generalises.  Otherwise one more n-point transform and one pointwise step per chunk (a, b, c and a(omega x) are resident), and,
+ * blinded, the term's degree <= 5n + 3 adds to T_0 .. T_3 (one more lane-kernel).  Every check as for those calls; d_q_range must
+ * not overlap d_t or d_scratch. */
+pg_status pg_quotient_range(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *d_q_range, int blinded,
+                            const pg_scalar *alpha, const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n,
+                            const pg_scalar k[4], const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream);
 /* pg_poly_evaluate: d_out[j] = sum_{i < n} c_j[i] point^i for the n_cols columns c_j = d_coeffs + j * col_stride (device,
  * Montgomery form; 1 <= n <= 2^32, col_stride >= n; point^0 = 1, so point = 0 gives c_j[0]).  A bad n or stride, a NULL or
  * misaligned pointer, or a point not reduced below the modulus -> PG_ERR_INVALID_ARGUMENT with nothing launched; otherwise

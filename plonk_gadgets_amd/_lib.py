@@ -190,6 +190,8 @@ SIGNATURES = {
     "pg_composer_conditionally_select_zero_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_composer_conditionally_select_one_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_composer_maybe_equal_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
+    "pg_composer_range_gate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
+    "pg_composer_range_gate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "pg_composer_max_bound_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_composer_range_check_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                                        C.c_void_p]),
@@ -220,6 +222,8 @@ SIGNATURES = {
                               _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_quotient_blinded": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), _P(Scalar), _P(Scalar), _P(Scalar), _P(Scalar),
                                       _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_quotient_range": (C.c_int, [C.c_void_p, C.c_uint32, _P(QuotientPolysC), C.c_void_p, C.c_int, _P(Scalar), _P(Scalar), _P(Scalar),
+                                    _P(Scalar), _P(Scalar), _P(Scalar), C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_poly_evaluate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p]),
     "pg_msm": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_msm_segmented": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, _P(C.c_uint64), C.c_uint64,

@@ -238,6 +238,17 @@ class StandardComposer:
     def maybe_equal_batch(self, a_vars: torch.Tensor, b_vars: torch.Tensor) -> torch.Tensor:
         return self._two_input_batch("pg_composer_maybe_equal_batch", a_vars, b_vars)
 
+    def range_gate(self, witness: int, num_bits: int) -> None:
+        """witness < 2^num_bits (num_bits even, 2..254) by the three-wire quad-accumulator widget: ceil(num_bits / 6) + 1 rows,
+        num_bits / 2 - 1 new Variables (the accumulators, which follow one another from the composer's end)"""
+        _chk(self._lib.pg_composer_range_gate(self._h, int(witness), int(num_bits)), "pg_composer_range_gate")
+
+    def range_gate_batch(self, witness_vars: torch.Tensor, num_bits: int) -> None:
+        """for v in witness_vars (existing Variables): range_gate(v, num_bits)"""
+        assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.dim() == 1 and witness_vars.is_contiguous()
+        _chk(self._lib.pg_composer_range_gate_batch(self._h, witness_vars.data_ptr(), int(num_bits), witness_vars.shape[0]),
+             "pg_composer_range_gate_batch")
+
     def max_bound_ragged_batch(self, max_range: torch.Tensor, witness: torch.Tensor):
         """for i: allocate(witness[i]); max_bound(max_range[i], w) -> (result Variables, num_bits per item)"""
         for x in (max_range, witness):
@@ -485,7 +496,7 @@ class StandardComposer:
         padded_n = self._padded_n(padded_n)
         return VerifierKey(padded_n, self.preprocessed_commitments(ck, padded_n))
 
-    NON_ARITHMETIC_SELECTORS = ("q_range", "q_logic", "q_fixed_group_add", "q_variable_group_add")
+    NON_ARITHMETIC_SELECTORS = ("q_logic", "q_fixed_group_add", "q_variable_group_add")  # the widgets the quotient leaves out
 
     def prover_polynomials(self, beta, gamma, padded_n: int | None = None, tail: int = 0) -> dict:
         """the 17 inputs of Engine.quotient as coefficients over the padded domain, keyed by its arguments: wires
@@ -493,8 +504,10 @@ class StandardComposer:
         Engine.QUOTIENT_SELECTORS) and pi (public_input_polynomial).  Nothing refers to the composer afterwards, so it may be
         closed before the quotient is computed.  tail: that many zero rows behind every wire column and behind z (wires
         int64[4, padded_n + tail, 4], z int64[padded_n + tail, 4]; their first padded_n rows are transformed in place), the room
-        Engine.blind needs; 0 by default.  Raises ValueError if a selector of the widgets the quotient leaves out (range,
-        logic, fixed- and variable-base group additions) is not zero, and NonExistingInverse as the grand product does."""
+        Engine.blind needs; 0 by default.  A circuit with range_gate items has an eighteenth input, "q_range" (int64[padded_n, 4]),
+        which Engine.quotient takes under that name; without such items the key is absent.  Raises ValueError if a selector of the
+        widgets the quotient leaves out (logic, fixed- and variable-base group additions) is not zero, and NonExistingInverse as
+        the grand product does."""
         n, padded_n = self.circuit_size(), self._padded_n(padded_n)
         assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
         dev = self.engine.device
@@ -502,7 +515,14 @@ class StandardComposer:
         for name in self.NON_ARITHMETIC_SELECTORS:
             _chk(self._lib.pg_composer_materialize(self._h, C.byref(_lib.FullColumnsC(**{name: buf.data_ptr()}))), "materialize")
             if bool(buf.any()):
-                raise ValueError(f"{name} is not zero: the quotient covers the arithmetic gate and the copy permutation only")
+                raise ValueError(f"{name} is not zero: the quotient covers the arithmetic gate, the range widget and the copy "
+                                 "permutation only")
+        _chk(self._lib.pg_composer_materialize(self._h, C.byref(_lib.FullColumnsC(q_range=buf.data_ptr()))), "materialize")
+        q_range = None
+        if bool(buf.any()):
+            q_range = torch.zeros((padded_n, 4), dtype=torch.int64, device=dev)
+            q_range[:n] = buf
+            self.engine.ifft(q_range, inplace=True)
         del buf
         names = self.engine.QUOTIENT_SELECTORS
         sel = torch.zeros((len(names), padded_n, 4), dtype=torch.int64, device=dev)
@@ -524,8 +544,11 @@ class StandardComposer:
         sigmas = self.engine.sigma_evaluations(sigma)
         del sigma
         self.engine.ifft(sigmas, inplace=True)
-        return {"wires": wires, "z": z, "sigmas": sigmas, "selectors": {name: sel[i] for i, name in enumerate(names)},
-                "pi": self.public_input_polynomial(padded_n)}
+        out = {"wires": wires, "z": z, "sigmas": sigmas, "selectors": {name: sel[i] for i, name in enumerate(names)},
+               "pi": self.public_input_polynomial(padded_n)}
+        if q_range is not None:
+            out["q_range"] = q_range
+        return out
 
     def quotient_polynomial(self, alpha, beta, gamma, padded_n: int | None = None) -> torch.Tensor:
         """the quotient polynomial t as int64[4, padded_n, 4] (t_lo, t_mid, t_hi, t_4th): Engine.quotient of prover_polynomials()"""
@@ -542,7 +565,8 @@ class StandardComposer:
         zero-knowledge up to the quotient's parts, which are not blinded; a sequence of 11 integers below r (a1 a0 b1 b0 c1 c0 d1
         d0 z2 z1 z0) is used as given, for tests.  The proof is an ordinary 1040-byte proof either way.  A blinded proof needs a
         circuit padded to at least 8 rows (ValueError) and a key of at least padded_n + 8 powers.  Raises PolynomialDegreeTooLarge
-        when the padded circuit exceeds the key, ValueError for the widgets the quotient leaves out."""
+        when the padded circuit exceeds the key, ValueError for the widgets the quotient leaves out (range_gate items are
+        proven: DESIGN section 3.19)."""
         from .proof import prove
         return prove(self, ck, label, preprocessed, timings, blinding)
 

@@ -23,6 +23,7 @@
 #include "emit.hpp"
 #include "fr.hpp"
 #include "range_gadgets.hpp"
+#include "range_gate.hpp"
 #include "scalar_gadgets.hpp"
 #include "composer.hpp"
 #include "permutation.hpp"
@@ -400,6 +401,21 @@ pg_status launch(pg_engine *e, const typename GD::Args &A, const pg_columns *c, 
         }
         return PG_OK;
     }
+}
+
+// a uniform gadget without inverses in the emitter mode the caller names: one launch on the caller's stream
+template <class GD, int MODE>
+pg_status launch_mode(pg_engine *e, const typename GD::Args &A, const pg_columns *c, uint64_t batch, uint64_t gate_base, uint64_t var_base,
+                      uint64_t zero_var, void *stream) {
+    static_assert(GD::kInv == 0 && !GD::kRagged && !pg::Split<GD>::ok, "one launch, no pre-pass, no prefix sums");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
+    const pg::EmitOut O = make_out(c, batch, GD::W, gate_base, var_base, zero_var, nullptr, nullptr);
+    const uint32_t max_blocks = (uint32_t)e->num_cus * (MODE == pg::EMIT_VALUES ? PG_GRID_BLOCKS_PER_CU : PG_EMIT_GRID_BLOCKS_PER_CU);
+    hipLaunchKernelGGL((pg::emit_kernel<GD, MODE>), dim3(O.tiles < max_blocks ? O.tiles : max_blocks), dim3(pg::kThreads), 0, st, A, O);
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
 }
 
 pg_status scalar_args(const pg_variable *a_var, const pg_scalar *a_val, const pg_variable *b_var,
@@ -954,6 +970,32 @@ static pg_status two_input_common(pg_engine *e, const pg_variable *d_a_var, cons
     return launch<GD>(e, A, out, batch, gate_base, var_base, 0, nullptr, nullptr, stream, nullptr, values_only);
 }
 
+// the range widget (range_gate.hpp) on existing Variables: num_bits even, 2 .. 254 (checked by the caller).  An item of
+// num_bits = 2 creates no Variable: its rows alone (EMIT_STRUCTURE: they are a function of the call), nothing when values_only.
+static pg_status range_gate_common(pg_engine *e, const pg_variable *d_witness_var, const pg_scalar *d_witness_val, uint32_t num_bits,
+                                   uint64_t batch, uint64_t gate_base, uint64_t var_base, uint64_t zero_var, const pg_columns *out,
+                                   void *stream, bool values_only) {
+    using GD = pg::RangeGateGD;
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "engine is NULL");
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+    PG_TRY(check_scalars(d_witness_val, "witness value array"));
+    PG_TRY(check_columns(out));
+    if ((batch + GD::W - 1) / GD::W > 0xffffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "batch too large for one call");
+    pg::RangeGateArgs A;
+    A.witness_vars = d_witness_var;
+    A.witness = reinterpret_cast<const uint4 *>(d_witness_val);
+    A.k = num_bits / 2;
+    A.g = (A.k + 2) / 3;
+    A.pad = 3 * A.g - A.k;
+    if (A.k == 1) {
+        if (values_only) return PG_OK;
+        return launch_mode<GD, pg::EMIT_STRUCTURE>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+    }
+    if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+    return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+}
+
 extern "C" {
 
 pg_status pg_conditionally_select_zero_batch(pg_engine *e, const pg_variable *d_x_var, const pg_scalar *d_x_val,
@@ -1454,17 +1496,18 @@ void quotient_step(const pg_engine *e, const pg::QuotientChunk &A, hipStream_t s
 // 4n + 8: QS_BLIND after each chunk's five wire / z transforms and quotient_top_kernel after the combine)
 pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *alpha, const pg_scalar *beta,
                            const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4], const pg_scalar *coset_gen,
-                           pg_scalar *d_t, pg_scalar *d_scratch, void *stream, bool blinded) {
+                           pg_scalar *d_t, pg_scalar *d_scratch, void *stream, bool blinded, const pg_scalar *q_range = nullptr) {
     if (!e || !p || !k) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
     if (log2_n > 30) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n > 30");
     if (blinded && log2_n < 3) return fail(PG_ERR_INVALID_ARGUMENT, "log2_n < 3: the blinders' rows would meet the top rows");
     const uint32_t m = log2_n;
     const uint64_t n = 1ull << m, col_bytes = n * sizeof(pg_scalar);
-    // the inputs in the order the chunks consume them; pi (the last) may be NULL
-    const pg_scalar *in[17] = {p->w[0], p->w[1], p->w[2], p->w[3], p->z, p->q_m, p->q_l, p->q_r, p->q_o, p->q_4,
-                               p->q_c, p->q_arith, p->sigma[0], p->sigma[1], p->sigma[2], p->sigma[3], p->pi};
+    // the inputs in the order the chunks consume them; pi and q_range (pg_quotient_range alone) may be NULL
+    const pg_scalar *in[18] = {p->w[0], p->w[1], p->w[2], p->w[3], p->z, p->q_m, p->q_l, p->q_r, p->q_o, p->q_4,
+                               p->q_c, p->q_arith, p->sigma[0], p->sigma[1], p->sigma[2], p->sigma[3], p->pi, q_range};
     for (int i = 0; i < 16; i++) PG_TRY(check_scalars(in[i], "an input polynomial"));
     if (p->pi) PG_TRY(check_scalars(p->pi, "pi"));
+    if (q_range) PG_TRY(check_scalars(q_range, "q_range"));
     PG_TRY(check_scalars(d_t, "d_t"));
     PG_TRY(check_scalars(d_scratch, "d_scratch"));
     PG_TRY(check_field(alpha, "alpha"));
@@ -1480,7 +1523,7 @@ pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_poly
         return fail(PG_ERR_INVALID_ARGUMENT, "coset_gen is zero or coset_gen^(4n) = 1: the coset meets H");
     const uint64_t t_bytes = 4 * col_bytes + (blinded ? 8 * sizeof(pg_scalar) : 0), s_bytes = PG_QUOTIENT_SCRATCH_COLS * col_bytes;
     if (overlaps(d_t, t_bytes, d_scratch, s_bytes)) return fail(PG_ERR_INVALID_ARGUMENT, "d_t overlaps d_scratch");
-    for (int i = 0; i < 17; i++) {
+    for (int i = 0; i < 18; i++) {
         const pg_scalar *x = in[i];
         const uint64_t x_bytes = col_bytes + (blinded && i < 5 ? (i < 4 ? 2 : 3) * sizeof(pg_scalar) : 0);  // the tails of w[j] and z
         if (x && (overlaps(d_t, t_bytes, x, x_bytes) || overlaps(d_scratch, s_bytes, x, x_bytes)))
@@ -1506,6 +1549,10 @@ pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_poly
     for (int j = 0; j < 4; j++) A.beta_k[j] = pg::fr_mul(A.beta, to_fr(&k[j]));
     A.n_fr = pg::fr_from_u64(n);
     const pg::Fr alpha2 = pg::fr_mul(A.alpha, A.alpha);
+    pg::QuotientRange Rg{};
+    Rg.alpha[0] = pg::fr_mul(alpha2, A.alpha);
+    Rg.alpha[1] = pg::fr_mul(Rg.alpha[0], A.alpha);
+    Rg.alpha[2] = pg::fr_mul(Rg.alpha[1], A.alpha);
     if (blinded)
         for (int i = 0; i < 5; i++) A.tail[i] = reinterpret_cast<const uint4 *>(in[i]) + 2 * n;
     pg::Fr g_j = g, zeta_jn = pg::fr_one();  // g zeta^j, zeta^(jn)
@@ -1531,6 +1578,10 @@ pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_poly
         quotient_step<pg::QS_GATE2>(e, A, st);
         PG_TRY(fwd(10, 6)); PG_TRY(fwd(11, 7));  // q_c, q_arith
         quotient_step<pg::QS_GATE3>(e, A, st);
+        if (q_range) {  // the range widget's term: q_range through column 5, which is free until QS_PERM1's inputs arrive
+            PG_TRY(fwd(17, 5));
+            hipLaunchKernelGGL(pg::quotient_range_kernel, dim3(grid_of(e, n, 8)), dim3(pg::kThreads), 0, st, A, Rg);
+        }
         if (p->pi) PG_TRY(fwd(16, 5));
         PG_TRY(fwd(12, 6)); PG_TRY(fwd(13, 7));  // sigma_1, sigma_2
         quotient_step<pg::QS_PERM1>(e, A, st);
@@ -1568,6 +1619,21 @@ pg_status quotient_enqueue(pg_engine *e, uint32_t log2_n, const pg_quotient_poly
         Tp.zw[0] = pg::fr_mul(omega, omega);
         for (uint32_t d = 3; d < pg::kQTop; d++) Tp.zw[d] = pg::fr_mul(Tp.zw[d - 1], omega_inv);
         hipLaunchKernelGGL(pg::quotient_top_kernel, dim3(1), dim3(pg::kQTopLanes), 0, st, Tp);
+        if (q_range) {
+            pg::QuotientRangeTop Rt{};
+            for (int j = 0; j < 3; j++) Rt.w[j] = reinterpret_cast<const uint4 *>(p->w[j]);
+            Rt.q_range = reinterpret_cast<const uint4 *>(q_range);
+            Rt.t = T;
+            Rt.n = n;
+            for (int j = 0; j < 3; j++) Rt.alpha[j] = Rg.alpha[j];
+            Rt.g4n = Tp.g4n;
+            // omega^(n + 1 - d) = omega, 1, omega^-1, omega^-2
+            Rt.aw[0] = omega;
+            Rt.aw[1] = pg::fr_one();
+            Rt.aw[2] = omega_inv;
+            Rt.aw[3] = pg::fr_mul(omega_inv, omega_inv);
+            hipLaunchKernelGGL(pg::quotient_range_top_kernel, dim3(1), dim3(pg::kQTopLanes), 0, st, Rt);
+        }
     }
     PG_HIP_TRY(hipGetLastError());
     return PG_OK;
@@ -1587,6 +1653,12 @@ pg_status pg_quotient_blinded(pg_engine *e, uint32_t log2_n, const pg_quotient_p
                               const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n, const pg_scalar k[4],
                               const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
     return quotient_enqueue(e, log2_n, p, alpha, beta, gamma, omega_4n, k, coset_gen, d_t, d_scratch, stream, true);
+}
+
+pg_status pg_quotient_range(pg_engine *e, uint32_t log2_n, const pg_quotient_polys *p, const pg_scalar *d_q_range, int blinded,
+                            const pg_scalar *alpha, const pg_scalar *beta, const pg_scalar *gamma, const pg_scalar *omega_4n,
+                            const pg_scalar k[4], const pg_scalar *coset_gen, pg_scalar *d_t, pg_scalar *d_scratch, void *stream) {
+    return quotient_enqueue(e, log2_n, p, alpha, beta, gamma, omega_4n, k, coset_gen, d_t, d_scratch, stream, blinded != 0, d_q_range);
 }
 
 pg_status pg_poly_evaluate(pg_engine *e, const pg_scalar *d_coeffs, uint64_t n_cols, uint64_t col_stride, uint64_t n,

@@ -23,6 +23,8 @@ struct pg_composer {
     std::vector<uint64_t> pi_gate;
     std::vector<pg_scalar> pi_val;
     std::vector<pg::FourthWire> fourth;
+    // the rows of the range widget (range_gate.hpp): where q_range = 1 (host list; written by materialize, checked by check)
+    std::vector<pg::RangeSeg> range_segs;
     // footprints of the batched calls (permutation.hpp) and the grow-only scratch of pg_composer_permutation
     std::vector<pg::PermSeg> segs;
     Scratch perm_small, perm_big, val_ws;  // val_ws: gathered assignments of batched calls
@@ -624,6 +626,7 @@ pg_status pg_composer_clear_witness(pg_composer *c) {
     c->pi_gate.clear();
     c->pi_val.clear();
     c->fourth.resize(c->fourth0);
+    c->range_segs.clear();
     c->segs.clear();
     c->sparse_hint = 0;
     c->last_kind = 0;
@@ -1118,7 +1121,61 @@ pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, con
 }
 }  // namespace
 
+// the range widget on existing Variables (range_gate.hpp): assignments gathered from the composer's own table, then the emitter.  The
+// rows leave no footprint (sigma and the wire values take the generic routes); the composer remembers where q_range = 1.
+namespace {
+pg_status range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    if (num_bits < 2 || num_bits > 254 || (num_bits & 1))
+        return fail(PG_ERR_INVALID_ARGUMENT, "range_gate: num_bits must be even and in [2, 254], got " + std::to_string(num_bits));
+    const uint32_t k = (uint32_t)num_bits / 2, g = (k + 2) / 3;
+    const uint64_t rows = (uint64_t)(g + 1) * batch, vars = (uint64_t)(k - 1) * batch;
+    PG_TRY(flush(c));
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+    pg_composer::Sig dg;
+    PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
+    PG_TRY(need(c, rows, vars));
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
+    uint4 *val = c->val_ws.as<uint4>();
+    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
+    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_witness_var, c->cols.view().vars, batch, val);
+    PG_HIP_TRY(hipGetLastError());
+    const pg_columns at = cols_at(c, c->n, c->nvars);
+    // (the rows: the Variable array, the bound and where the call lands)
+    SignedAppend sa(c, gadget_sig(c, 27, pg::fr_zero(), pg::fr_zero(), batch, num_bits, dg), rows);
+    PG_TRY(range_gate_common(c->e, d_witness_var, reinterpret_cast<const pg_scalar *>(val), (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var,
+                             &at, c->stream, sa.in_place));
+    sa.commit();
+    pg::RangeSeg *last = c->range_segs.empty() ? nullptr : &c->range_segs.back();
+    if (last && last->g == g && last->first + last->items * (g + 1) == c->n) last->items += batch;
+    else c->range_segs.push_back(pg::RangeSeg{c->n, batch, g});
+    c->n += rows;
+    c->nvars += vars;
+    return PG_OK;
+}
+}  // namespace
+
 extern "C" {
+
+pg_status pg_composer_range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
+    return range_gate_batch(c, d_witness_var, num_bits, batch);
+}
+// a batch of one: the Variable goes through the composer's staging words
+pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t num_bits) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    if (num_bits < 2 || num_bits > 254 || (num_bits & 1))
+        return fail(PG_ERR_INVALID_ARGUMENT, "range_gate: num_bits must be even and in [2, 254], got " + std::to_string(num_bits));
+    PG_TRY(flush(c));
+    PG_TRY(check_var(c, witness));
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    pg::StageBlob b{};
+    b.w[0] = witness;
+    PG_TRY(stage(c, b, 1));
+    return range_gate_batch(c, c->stage_words(), num_bits, 1);
+}
 
 pg_status pg_composer_conditionally_select_zero_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_select_var,
                                                       uint64_t batch, pg_variable *d_result_vars) {
@@ -1446,6 +1503,12 @@ pg_status pg_composer_check(pg_composer *c, int64_t *first_bad) {
     const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 8 ? (want ? want : 1) : (uint64_t)c->e->num_cus * 8);
     hipLaunchKernelGGL(pg::check_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, c->cols.view(), c->n, (uint64_t)0, c->nvars,
                        c->zero_var, d_gate, d_val, (uint32_t)c->pi_gate.size(), d_fw, (uint32_t)c->fourth.size(), d_bad);
+    // the range widget's rows: the minimum over both kinds of failure
+    for (const pg::RangeSeg &s : c->range_segs) {
+        const uint64_t rw = (s.items * s.g + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
+        hipLaunchKernelGGL(pg::range_check_rows_kernel, dim3((uint32_t)(rw < most ? rw : most)), dim3(pg::kThreads), 0, c->stream, c->cols.view(), s,
+                           c->nvars, d_bad);
+    }
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipMemcpyAsync(&h_bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -1541,6 +1604,12 @@ pg_status pg_composer_materialize(pg_composer *c, const pg_full_columns *out) {
     if (d_fw)
         hipLaunchKernelGGL(pg::patch_fourth_kernel, dim3(1), dim3(64), 0, c->stream, reinterpret_cast<uint4 *>(out->q_4), out->w_4,
                            reinterpret_cast<uint4 *>(out->w_4_value), c->cols.view().vars, d_fw, (uint32_t)c->fourth.size());
+    if (out->q_range)  // the range widget's rows, over the zeros of the passes above
+        for (const pg::RangeSeg &s : c->range_segs) {
+            const uint64_t rw = (2 * s.items * s.g + pg::kThreads - 1) / pg::kThreads;
+            hipLaunchKernelGGL(pg::range_patch_kernel, dim3((uint32_t)(rw < grid ? rw : grid)), dim3(pg::kThreads), 0, c->stream,
+                               reinterpret_cast<uint4 *>(out->q_range), s);
+        }
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
     return PG_OK;

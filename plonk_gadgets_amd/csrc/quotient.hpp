@@ -247,6 +247,85 @@ __global__ __launch_bounds__(kQTopLanes) void quotient_top_kernel(const Quotient
     for (uint32_t k = 0; k < kQTop; k++) pp_store(A.t, k, fr_sub(pp_load(A.t, k), fr_mul(A.g4n, pp_load(A.t, 4 * n + k))));
 }
 
+// ---- the range widget's term (pg_quotient_range) ------------------------------------------------------------
+//   N(x) += q_range(x) [ alpha^3 delta(b - 4a) + alpha^4 delta(c - 4b) + alpha^5 delta(a(omega x) - 4c) ],  delta(f) = f (f-1)(f-2)(f-3)
+// a, b and c are resident in scratch columns 0..2 (blinded already, when the call is), a(omega x) is entry (i + 1) mod n of column 0 as
+// z(omega x) is of column 4, and q_range has just been transformed into column 5.  The step runs after QS_GATE3 and before QS_PERM1
+// (which reuses column 5): t is still N's partial sum, not yet divided by c_j.
+struct QuotientRange {
+    Fr alpha[3];  // alpha^3, alpha^4, alpha^5
+};
+__device__ __forceinline__ Fr range_delta(const Fr &hi, const Fr &lo) {  // delta(hi - 4 lo)
+    const Fr two = fr_add(lo, lo), f = fr_sub(hi, fr_add(two, two)), one = fr_one();
+    const Fr f1 = fr_sub(f, one), f2 = fr_sub(f1, one), f3 = fr_sub(f2, one);
+    return fr_mul(fr_mul(f, f1), fr_mul(f2, f3));
+}
+__global__ __launch_bounds__(kThreads) void quotient_range_kernel(const QuotientChunk A, const QuotientRange G) {
+    for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < A.n; i += (uint64_t)gridDim.x * kThreads) {
+        const Fr a = q_col(A, 0, i), b = q_col(A, 1, i), c = q_col(A, 2, i), aw = q_col(A, 0, (i + 1) & (A.n - 1));
+        Fr s = fr_mul(G.alpha[0], range_delta(b, a));
+        s = fr_add(s, fr_mul(G.alpha[1], range_delta(c, b)));
+        s = fr_add(s, fr_mul(G.alpha[2], range_delta(aw, c)));
+        pp_store(A.t, i, fr_add(pp_load(A.t, i), fr_mul(q_col(A, 5, i), s)));
+    }
+}
+
+// Blinded: the term has degree <= (n - 1) + 4 (n + 1) = 5n + 3, so it adds to T_0 .. T_3: the truncated product of the top four
+// coefficients of q_range (rows n-1 .. n-4) and of the four factors of each delta, which share theirs (rows n+1 .. n-2 of hi - 4 lo,
+// times omega^row for a(omega X); the constants 1, 2, 3 lie in row 0, below the windows for n >= 8).  One working lane, after
+// quotient_top_kernel, whose correction is linear: t[4n + i] += X_i and t[i] -= g^(4n) X_i.
+constexpr uint32_t kQRangeTop = 4;
+struct QuotientRangeTop {
+    const uint4 *w[3], *q_range;  // the caller's a, b, c (n + 2 rows) and q_range (n rows)
+    uint4 *t;                     // 4n + 8 rows
+    uint64_t n;
+    Fr alpha[3], g4n;
+    Fr aw[kQRangeTop];            // omega^(n + 1 - d): a(omega X)'s coefficient d below the top is a's times this
+};
+__device__ __forceinline__ void quotient_range_top_mul(Fr (&acc)[kQRangeTop], const Fr (&b)[kQRangeTop]) {
+#pragma unroll
+    for (int d = (int)kQRangeTop - 1; d >= 0; d--) {
+        Fr p = fr_mul(acc[0], b[d]);
+#pragma unroll
+        for (int d1 = 1; d1 <= d; d1++) p = fr_add(p, fr_mul(acc[d1], b[d - d1]));
+        acc[d] = p;
+    }
+}
+__global__ __launch_bounds__(kQTopLanes) void quotient_range_top_kernel(const QuotientRangeTop A) {
+    if (blockIdx.x | threadIdx.x) return;
+    const uint64_t n = A.n;
+    Fr q[kQRangeTop], X[kQRangeTop];
+#pragma unroll
+    for (uint32_t d = 0; d < kQRangeTop; d++) {
+        q[d] = pp_load(A.q_range, n - 1 - d);
+        X[d] = fr_zero();
+    }
+#pragma unroll 1
+    for (uint32_t s = 0; s < 3; s++) {
+        const uint4 *lo = A.w[s], *hi = A.w[s == 2 ? 0 : s + 1];
+        Fr f[kQRangeTop], acc[kQRangeTop];
+#pragma unroll
+        for (uint32_t d = 0; d < kQRangeTop; d++) {
+            Fr h = pp_load(hi, n + 1 - d);
+            if (s == 2) h = fr_mul(h, A.aw[d]);
+            const Fr l = pp_load(lo, n + 1 - d), two = fr_add(l, l);
+            f[d] = fr_sub(h, fr_add(two, two));
+            acc[d] = f[d];
+        }
+#pragma unroll 1
+        for (uint32_t k = 0; k < 3; k++) quotient_range_top_mul(acc, f);
+        quotient_range_top_mul(acc, q);
+#pragma unroll
+        for (uint32_t d = 0; d < kQRangeTop; d++) X[d] = fr_add(X[d], fr_mul(A.alpha[s], acc[d]));
+    }
+#pragma unroll
+    for (uint32_t d = 0; d < kQRangeTop; d++) {
+        const uint64_t i = kQRangeTop - 1 - d;  // acc[d] = the coefficient 5n + 3 - d
+        pp_store(A.t, 4 * n + i, fr_add(pp_load(A.t, 4 * n + i), X[d]));
+        pp_store(A.t, i, fr_sub(pp_load(A.t, i), fr_mul(A.g4n, X[d])));
+    }
+}
+
 // ---- evaluation at a point ----------------------------------------------------------------------------------------------------
 struct PolyEval {
     const uint4 *c;          // column j at c + 2 j stride

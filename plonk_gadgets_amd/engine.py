@@ -563,14 +563,32 @@ class Engine:
         """rows of 4 contiguous limbs on the device"""
         return t.is_cuda and t.dtype == torch.int64 and t.shape[-1] == 4 and t.stride(-1) == 1 and t.stride(-2) == 4
 
+    def _quotient_call(self, blinded: bool, log2_n, p, q_range, alpha, beta, gamma, zeta, ks, g, out, scratch):
+        """pg_quotient / pg_quotient_blinded, or pg_quotient_range when the range widget's selector polynomial is given"""
+        n = 1 << log2_n
+        args = (C.byref(_field(alpha).c), C.byref(_field(beta).c), C.byref(_field(gamma).c), C.byref(zeta.c), ks, C.byref(_field(g).c),
+                out.data_ptr(), scratch.data_ptr(), self._stream())
+        if q_range is None:
+            name = "pg_quotient_blinded" if blinded else "pg_quotient"
+            st = getattr(self._lib, name)(self._h, log2_n, C.byref(p), *args)
+        else:
+            if not (self._rows(q_range) and q_range.dim() == 2 and q_range.shape[0] == n):
+                raise ValueError(f"q_range must be int64[{n}, 4] on the device with contiguous rows")
+            name = "pg_quotient_range"
+            st = self._lib.pg_quotient_range(self._h, log2_n, C.byref(p), q_range.data_ptr(), int(blinded), *args)
+        if st != 0:
+            raise PgError(st, name)
+        return out
+
     def quotient(self, wires, z, sigmas, selectors: dict, pi=None, *, alpha, beta, gamma, omega_4n=None, k=DEFAULT_K,
-                 g=DEFAULT_COSET_GENERATOR, scratch=None) -> torch.Tensor:
+                 g=DEFAULT_COSET_GENERATOR, scratch=None, q_range=None) -> torch.Tensor:
         """PLONK's quotient polynomial t (pg_quotient, the prover's round 3 for the arithmetic gate, the public inputs and the copy
         permutation) as int64[4, n, 4]: t_lo, t_mid, t_hi, t_4th.  Every input is a polynomial of n = 2^m coefficients
         (int64[n, 4] on the device; wires and sigmas: four of them, or int64[4, n, 4]); selectors: QUOTIENT_SELECTORS -> tensor;
         pi None is the zero polynomial.  omega_4n defaults to domain_generator(m + 2) (whose fourth power is the domain's omega);
         scratch: int64[PG_QUOTIENT_SCRATCH_COLS = 8, n, 4] the call may overwrite (allocated if None).
-        StandardComposer.prover_polynomials() gives all of them."""
+        StandardComposer.prover_polynomials() gives all of them.  q_range (int64[n, 4], None: none): the selector polynomial of the
+        range widget, whose term joins N (pg_quotient_range)."""
         polys = [wires[j] for j in range(4)] + [z] + [sigmas[j] for j in range(4)] + [selectors[s] for s in self.QUOTIENT_SELECTORS]
         n = polys[0].shape[0]
         if n < 1 or n & (n - 1) or n > 1 << 30:
@@ -594,19 +612,15 @@ class Engine:
         p.pi = None if pi is None else pi.data_ptr()
         zeta = domain_generator(log2_n + 2) if omega_4n is None else _field(omega_4n)
         ks = (_lib.Scalar * 4)(*[_field(x).c for x in k])
-        st = self._lib.pg_quotient(self._h, log2_n, C.byref(p), C.byref(_field(alpha).c), C.byref(_field(beta).c),
-                                   C.byref(_field(gamma).c), C.byref(zeta.c), ks, C.byref(_field(g).c), out.data_ptr(),
-                                   scratch.data_ptr(), self._stream())
-        if st != 0:
-            raise PgError(st, "pg_quotient")
-        return out
+        return self._quotient_call(False, log2_n, p, q_range, alpha, beta, gamma, zeta, ks, g, out, scratch)
 
     def quotient_blinded(self, wires, z, sigmas, selectors: dict, pi=None, *, alpha, beta, gamma, omega_4n=None, k=DEFAULT_K,
-                         g=DEFAULT_COSET_GENERATOR, scratch=None) -> torch.Tensor:
+                         g=DEFAULT_COSET_GENERATOR, scratch=None, q_range=None) -> torch.Tensor:
         """the quotient polynomial of BLINDED wire and permutation polynomials (pg_quotient_blinded) as one
         int64[4n + 8, 4]: the prover's parts are the views [0:n], [n:2n], [2n:3n] and [3n:4n + 8] (t_4th has n + 8 rows, the last
         one zero).  wires: int64[4, n + 2, 4] or four int64[n + 2, 4] (views of longer columns will do), z: int64[n + 3, 4], blinded
-        as blind() blinds them; everything else as for quotient(), n = 2^m >= 8 the length of the sigmas."""
+        as blind() blinds them; everything else as for quotient() (q_range, of n rows, included), n = 2^m >= 8 the length of the
+        sigmas."""
         polys = [wires[j] for j in range(4)] + [z] + [sigmas[j] for j in range(4)] + [selectors[s] for s in self.QUOTIENT_SELECTORS]
         n = polys[5].shape[0]
         if n < 8 or n & (n - 1) or n > 1 << 30:
@@ -632,12 +646,7 @@ class Engine:
         p.pi = None if pi is None else pi.data_ptr()
         zeta = domain_generator(log2_n + 2) if omega_4n is None else _field(omega_4n)
         ks = (_lib.Scalar * 4)(*[_field(x).c for x in k])
-        st = self._lib.pg_quotient_blinded(self._h, log2_n, C.byref(p), C.byref(_field(alpha).c), C.byref(_field(beta).c),
-                                           C.byref(_field(gamma).c), C.byref(zeta.c), ks, C.byref(_field(g).c), out.data_ptr(),
-                                           scratch.data_ptr(), self._stream())
-        if st != 0:
-            raise PgError(st, "pg_quotient_blinded")
-        return out
+        return self._quotient_call(True, log2_n, p, q_range, alpha, beta, gamma, zeta, ks, g, out, scratch)
 
     def blind(self, poly_ext: torch.Tensor, n: int, blinders) -> torch.Tensor:
         """poly_ext: int64[>= n + len(blinders), 4] on the device, rows 0..n-1 an interpolated polynomial and the rows behind them

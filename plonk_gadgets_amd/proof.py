@@ -7,8 +7,9 @@ but NOT zero-knowledge.  prove(..., blinding=True) blinds the four wire polynomi
 w_j + (b1 X + b0)(X^n - 1) and z + (b2 X^2 + b1 X + b0)(X^n - 1) (the PLONK paper's rounds 1 and 2; dusk-plonk 0.8 has none), so
 that the commitments and evaluations a proof reveals are those of blinded polynomials; the quotient's parts are not blinded
 separately (the paper's optional b10, b11 are left out).  The verifier does not change: a blinded proof is an ordinary proof.  The
-arithmetic gate, the public inputs and the copy permutation are proven; circuits that use the range, logic or group-addition
-widgets are refused (prover_polynomials)."""
+arithmetic gate, the public inputs, the copy permutation and the three-wire range widget (range_gate, DESIGN section 3.19: its
+term joins the quotient and r(X), no new evaluation or opening) are proven; circuits that use the logic or group-addition widgets
+are refused (prover_polynomials)."""
 from __future__ import annotations
 
 import secrets
@@ -109,6 +110,16 @@ def linearisation(ev: dict, alpha: int, beta: int, gamma: int, xi: int, n: int, 
         num = num * (w + beta * kj * xi + gamma) % R
     rho = [qa * a * b, qa * a, qa * b, qa * c, qa * d, qa, num + alpha * alpha * l1, -alpha * beta * ev["perm_eval"] * p3]
     return [x % R for x in rho]
+
+
+def range_rho(ev: dict, alpha: int) -> int:
+    """rho_range, the coefficient of q_range(X) in r(X) for a circuit with range_gate items:
+    alpha^3 delta(b - 4a) + alpha^4 delta(c - 4b) + alpha^5 delta(a_next - 4c), delta(f) = f (f - 1)(f - 2)(f - 3), from the
+    evaluations a, b, c at xi and a at xi omega"""
+    def delta(f):
+        return f * (f - 1) * (f - 2) * (f - 3) % R
+    a, b, c, an = (ev[f] for f in ("a_eval", "b_eval", "c_eval", "a_next_eval"))
+    return (pow(alpha, 3, R) * delta(b - 4 * a) + pow(alpha, 4, R) * delta(c - 4 * b) + pow(alpha, 5, R) * delta(an - 4 * c)) % R
 
 
 def _stacked(ts):
@@ -215,7 +226,7 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
     else:
         # t_1, t_2, t_3 of n rows and t_4 of n + 8, views of one int64[4n + 8, 4]
         tq = eng.quotient_blinded([pp["wires"][j, :padded_n + 2] for j in range(4)], pp["z"][:padded_n + 3], pp["sigmas"],
-                                  pp["selectors"], pp["pi"], alpha=S(alpha), beta=S(beta), gamma=S(gamma))
+                                  pp["selectors"], pp["pi"], alpha=S(alpha), beta=S(beta), gamma=S(gamma), q_range=pp.get("q_range"))
         ph.mark("round3_quotient")
         t = [tq[j * padded_n:(j + 1) * padded_n] for j in range(3)] + [tq[3 * padded_n:]]
         t_comm = ck.commit(tq[:3 * padded_n].view(3, padded_n, 4)) + [ck.commit(t[3])]
@@ -240,6 +251,10 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
     rho = linearisation(ev, alpha, beta, gamma, xi, padded_n)
     s_at_xi = [qe["q_m"], qe["q_l"], qe["q_r"], qe["q_o"], qe["q_4"], qe["q_c"], z_xi, se[3]]
     ev["lin_poly_eval"] = sum(r * s for r, s in zip(rho, s_at_xi)) % R
+    q_range = pp.get("q_range")  # range_gate items: r(X) gains rho_range q_range(X)
+    if q_range is not None:
+        rho_range = range_rho(ev, alpha)
+        ev["lin_poly_eval"] = (ev["lin_poly_eval"] + rho_range * eng.evaluate(q_range, xi)[0].to_int()) % R
     ph.mark("round4_evaluate")
     for f in EVALUATIONS:
         tr.append_scalar(f.encode(), ev[f])
@@ -261,6 +276,8 @@ def prove(composer, ck, label=b"plonk", preprocessed=None, timings: dict | None 
         put(s, sel[s], v * lin[s])
     put("z", z, v * lin["z"])
     put(("sigma", 3), sig[3], v * lin["fourth_sigma"])
+    if q_range is not None:
+        put("q_range", q_range, v * rho_range)
     opened = [sig[0], sig[1], sig[2], wires[0], wires[1], wires[2], wires[3], sel["q_arith"], sel["q_c"], sel["q_l"], sel["q_r"]]
     keys = [("sigma", 0), ("sigma", 1), ("sigma", 2), ("w", 0), ("w", 1), ("w", 2), ("w", 3), "q_arith", "q_c", "q_l", "q_r"]
     vi = v

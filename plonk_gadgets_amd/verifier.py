@@ -34,7 +34,7 @@ import torch
 from . import _lib
 from .engine import DEFAULT_K, PgError, domain_generator
 from .g1 import P, G1Affine, points_tensor
-from .proof import COMMITMENTS, EVALUATIONS, Proof
+from .proof import COMMITMENTS, EVALUATIONS, Proof, range_rho
 from .scalar import BlsScalar
 from .transcript import R, Transcript
 
@@ -200,9 +200,12 @@ def _as_ints(public_inputs) -> dict:
     return out
 
 
-def sides(proof: Proof, vk: VerifierKey, ok, public_inputs, label=b"plonk"):
+def sides(proof: Proof, vk: VerifierKey, ok, public_inputs, label=b"plonk", range_term: bool = False):
     """None when the proof is rejected before any pairing, else {point: [a, b]}: the check is
-    e(sum a P, [tau]_2) e(sum b P, [1]_2) = 1"""
+    e(sum a P, [tau]_2) e(sum b P, [1]_2) = 1.
+    range_term: r(X)'s term of the range widget, rho_range [q_range] from the key -- what verify, verify_each
+    and verify_batch ask for.  Without it (the default) the table is the one pg_plonk_sides builds, whose model this function is:
+    23 rows, none for q_range."""
     if not vk.valid:
         return None
     cm = {f: getattr(proof, f) for f in COMMITMENTS}
@@ -263,6 +266,10 @@ def sides(proof: Proof, vk: VerifierKey, ok, public_inputs, label=b"plonk"):
     for coeff, point in ((qa * a * b, pre["q_m"]), (qa * a, pre["q_l"]), (qa * b, pre["q_r"]), (qa * c, pre["q_o"]), (qa * d, pre["q_4"]),
                          (qa, pre["q_c"]), (zc + alpha * alpha * l1, cm["z_comm"]), (-alpha * beta * zw * p3, pre["fourth_sigma"])):
         put(point, 0, -v * coeff)
+    # a circuit with range_gate items: r gains rho_range [q_range].  A key whose q_range is the identity
+    # gets no row for it: its table is what it was
+    if range_term and not pre["q_range"].is_identity():
+        put(pre["q_range"], 0, -v * range_rho(ev, alpha))
     value = (t_eval + v * ev["lin_poly_eval"]) % R
     vi = v
     for point, f in ((pre["left_sigma"], "left_sigma_eval"), (pre["right_sigma"], "right_sigma_eval"), (pre["out_sigma"], "out_sigma_eval"),
@@ -327,7 +334,7 @@ def verify(proof: Proof, vk: VerifierKey, ok, public_inputs=None, label=b"plonk"
     """True iff the proof verifies under the verifier key vk and the OpeningKey ok, for the public inputs {row: value} (rows of
     the padded circuit; canonical integers or BlsScalars).  False -- never an exception -- for xi^n = 1, a commitment off the
     curve or outside the order-r subgroup, and any proof whose pairing check fails."""
-    table = sides(proof, vk, ok, public_inputs, label)
+    table = sides(proof, vk, ok, public_inputs, label, range_term=True)
     if table is None:
         return False
     # one segment of pg_msm_segmented, not pg_msm: 14.2 ms instead of 50.5 for these 22 points (DESIGN section 3.15,
@@ -347,7 +354,7 @@ def verify_each(proofs, vks, ok, public_inputs, label=b"plonk") -> list:
     vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
     out, tables, where = [False] * n, [], []
     for i, proof in enumerate(proofs):
-        table = sides(proof, vks[i], ok, pis[i], labels[i])
+        table = sides(proof, vks[i], ok, pis[i], labels[i], range_term=True)
         if table is not None:
             tables.append(table)
             where.append(i)
@@ -390,12 +397,16 @@ def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_s
     The answer is verify's, proof by proof, with one exception: a public-input row >= n.  sides / verify take omega^row for
     any row (row n is row 0 to them) and may accept; here such a proof is rejected with PG_SIDES_BAD_PUBLIC_INPUT.
     With return_status also the lists (status, where) of pg_plonk_sides (SIDES_STATUS names the values; a key that is not
-    valid gives PG_SIDES_BAD_KEY)."""
+    valid gives PG_SIDES_BAD_KEY).  ValueError also for a key whose q_range commitment is not the identity: pg_plonk_key has 11
+    points and the table 23 rows, none of them for the range widget's term."""
     engine = ok.engine
     n, data = _proof_bytes(proofs)
     if n == 0:
         return ([], [], []) if return_status else []
     vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
+    if any(not vk.commitments["q_range"].is_identity() for vk in vks):
+        raise ValueError("a key with a live q_range (range_gate items): pg_plonk_sides builds no row for the range term; "
+                         "use verify_each")
     table, records, key_index, bad_key = {}, [], [], []
     for i in range(n):
         k = (id(vks[i]), bytes(labels[i]))
@@ -466,7 +477,7 @@ def verify_batch(proofs, vks, ok, public_inputs, label=b"plonk") -> bool:
     vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
     folded = {}
     for i, proof in enumerate(proofs):
-        table = sides(proof, vks[i], ok, pis[i], labels[i])
+        table = sides(proof, vks[i], ok, pis[i], labels[i], range_term=True)
         if table is None:
             return False
         rho = 1 if i == 0 else secrets.randbits(128) | 1
