@@ -122,8 +122,11 @@ uint64_t pg_num_bits_closest_power_of_two(const pg_scalar *s); /* src/range.rs:1
  * device, 16-byte aligned buffers of 32 * batch bytes:
  *   from_canonical  BlsScalar::from_bytes per element; an encoding >= q (from_bytes returns Err) becomes 0, is flagged in
  *                   d_bad_mask (may be NULL) and counted; PG_ERR_BAD_ENCODING if any -- the output is complete all the
- *                   same -- while PG_ERR_INVALID_ARGUMENT keeps meaning a bad pointer (synchronises `stream`)
- *   to_canonical    BlsScalar::to_bytes per element */
+ *                   same -- while PG_ERR_INVALID_ARGUMENT keeps meaning a bad pointer (synchronises `stream`).  It counts
+ *                   in the engine's scratch, the plan calls' error count: like them it is ordered behind the engine's
+ *                   previous call on another stream, and the next one behind it.  The count comes back in a word of its
+ *                   own: what pg_plan_result reports of an earlier plan is left alone
+ *   to_canonical    BlsScalar::to_bytes per element; uses no engine scratch and takes no part in that ordering */
 pg_status pg_scalars_from_canonical_batch(pg_engine *e, const void *d_bytes, uint64_t batch, pg_scalar *d_out,
                                           uint8_t *d_bad_mask, uint64_t *bad_count /* may be NULL */, void *stream);
 pg_status pg_scalars_to_canonical_batch(pg_engine *e, const pg_scalar *d_scalars, uint64_t batch, void *d_bytes, void *stream);
@@ -664,7 +667,8 @@ pg_status pg_msm(pg_engine *e, const pg_g1_affine *d_bases, const pg_scalar *d_s
  * checked here and copied to the device (it is the caller's again when the call returns).  A bad seg_off, n = 0 with
  * n_segs > 0, n_cols = 0, a stride below n, n x n_cols >= 2^31 (or n_segs x n_cols >= 2^31), a NULL or misaligned pointer, or
  * d_out overlapping an input -> PG_ERR_INVALID_ARGUMENT with nothing launched; n_segs = 0 does nothing and is PG_OK;
- * otherwise the call only enqueues.
+ * otherwise the call only enqueues -- behind one host wait when the engine's previous pg_msm_segmented is still pending: seg_off
+ * is staged in one pinned buffer, which is rewritten only after the copy that last read it has left.
  * Every product s_j[i] P_i is a scalar multiplication on a lane of its own: 86 fixed windows of signed 3-bit digits over a
  * table 2P, 3P, 4P in LDS (255 doublings and up to 86 complete additions: about 3 500 Fq products per point and column,
  * whatever the scalar).  One wave per (segment, column) then sums the segment's products -- a segment of any length is

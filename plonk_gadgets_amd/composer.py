@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import ctypes as C
 import hashlib
+from contextlib import contextmanager
 from dataclasses import dataclass
 
 import torch
@@ -51,6 +52,23 @@ class StandardComposer:
         _chk(self._lib.pg_composer_create(engine._h, gate_capacity, var_capacity, int(with_dummy), engine._stream(),
                                           C.byref(h)), "pg_composer_create")
         self._h = h
+        self._stream = torch.cuda.current_stream(engine.device)  # the stream pg_composer_create bound the composer to
+
+    @contextmanager
+    def _hand_over(self):
+        """around every composer call that is given a device tensor: the composer's calls run on the stream it was made on,
+        the tensor is torch's current stream's.  Under another current stream the composer's stream first waits for it (the
+        tensor's producers, a zero fill among them, come first) and it then waits for the composer's stream (whoever reads
+        the tensor next comes after the call's kernels).  Nothing when the two are the same stream."""
+        cur = torch.cuda.current_stream(self.engine.device)
+        if cur == self._stream:
+            yield
+            return
+        self._stream.wait_stream(cur)
+        try:
+            yield
+        finally:
+            cur.wait_stream(self._stream)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -169,17 +187,19 @@ class StandardComposer:
         """for w in witness: allocate(w); range_check(min, max, w) -- appended at the composer's end"""
         assert witness.is_cuda and witness.dtype == torch.int64 and witness.dim() == 2 and witness.is_contiguous()
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
-        _chk(self._lib.pg_composer_range_check_batch(self._h, C.byref(min_range.c), C.byref(max_range.c),
-                                                     witness.data_ptr(), witness.shape[0], res.data_ptr()),
-             "pg_composer_range_check_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_range_check_batch(self._h, C.byref(min_range.c), C.byref(max_range.c),
+                                                         witness.data_ptr(), witness.shape[0], res.data_ptr()),
+                 "pg_composer_range_check_batch")
         return res
 
     def add_input_batch(self, scalars: torch.Tensor) -> int:
         """for s in scalars: add_input(s) -- returns the first Variable (the others follow it)"""
         assert scalars.is_cuda and scalars.dtype == torch.int64 and scalars.dim() == 2 and scalars.is_contiguous()
         first = C.c_uint64()
-        _chk(self._lib.pg_composer_add_input_batch(self._h, scalars.data_ptr(), scalars.shape[0], C.byref(first)),
-             "pg_composer_add_input_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_add_input_batch(self._h, scalars.data_ptr(), scalars.shape[0], C.byref(first)),
+                 "pg_composer_add_input_batch")
         return int(first.value)
 
     def range_check_allocated_batch(self, min_range: BlsScalar, max_range: BlsScalar, witness_vars: torch.Tensor,
@@ -188,9 +208,10 @@ class StandardComposer:
         assert witness.is_cuda and witness.dtype == torch.int64 and witness.dim() == 2 and witness.is_contiguous()
         assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.shape == (witness.shape[0],)
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
-        _chk(self._lib.pg_composer_range_check_allocated_batch(self._h, C.byref(min_range.c), C.byref(max_range.c),
-                                                               witness_vars.data_ptr(), witness.data_ptr(), witness.shape[0],
-                                                               res.data_ptr()), "pg_composer_range_check_allocated_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_range_check_allocated_batch(self._h, C.byref(min_range.c), C.byref(max_range.c),
+                                                                   witness_vars.data_ptr(), witness.data_ptr(), witness.shape[0],
+                                                                   res.data_ptr()), "pg_composer_range_check_allocated_batch")
         return res
 
     def max_bound_batch(self, max_range: BlsScalar, witness: torch.Tensor):
@@ -198,8 +219,9 @@ class StandardComposer:
         assert witness.is_cuda and witness.dtype == torch.int64 and witness.dim() == 2 and witness.is_contiguous()
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
         nb = C.c_uint64()
-        _chk(self._lib.pg_composer_max_bound_batch(self._h, C.byref(max_range.c), witness.data_ptr(), witness.shape[0],
-                                                   res.data_ptr(), C.byref(nb)), "pg_composer_max_bound_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_max_bound_batch(self._h, C.byref(max_range.c), witness.data_ptr(), witness.shape[0],
+                                                       res.data_ptr(), C.byref(nb)), "pg_composer_max_bound_batch")
         return res, int(nb.value)
 
     def max_bound_allocated_batch(self, max_range: BlsScalar, witness_vars: torch.Tensor, witness: torch.Tensor):
@@ -207,9 +229,10 @@ class StandardComposer:
         assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.shape == (witness.shape[0],)
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
         nb = C.c_uint64()
-        _chk(self._lib.pg_composer_max_bound_allocated_batch(self._h, C.byref(max_range.c), witness_vars.data_ptr(),
-                                                             witness.data_ptr(), witness.shape[0], res.data_ptr(), C.byref(nb)),
-             "pg_composer_max_bound_allocated_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_max_bound_allocated_batch(self._h, C.byref(max_range.c), witness_vars.data_ptr(),
+                                                                 witness.data_ptr(), witness.shape[0], res.data_ptr(), C.byref(nb)),
+                 "pg_composer_max_bound_allocated_batch")
         return res, int(nb.value)
 
     def scalar_decomposition_batch(self, num_bits: int, witness_vars: torch.Tensor, witness: torch.Tensor) -> torch.Tensor:
@@ -217,16 +240,18 @@ class StandardComposer:
         assert witness.is_cuda and witness.dtype == torch.int64 and witness.dim() == 2 and witness.is_contiguous()
         assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.shape == (witness.shape[0],)
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
-        _chk(self._lib.pg_composer_scalar_decomposition_batch(self._h, num_bits, witness_vars.data_ptr(), witness.data_ptr(),
-                                                              witness.shape[0], res.data_ptr()),
-             "pg_composer_scalar_decomposition_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_scalar_decomposition_batch(self._h, num_bits, witness_vars.data_ptr(), witness.data_ptr(),
+                                                                  witness.shape[0], res.data_ptr()),
+                 "pg_composer_scalar_decomposition_batch")
         return res
 
     def _two_input_batch(self, fn: str, a_vars: torch.Tensor, b_vars: torch.Tensor) -> torch.Tensor:
         assert a_vars.is_cuda and a_vars.dtype == torch.int64 and a_vars.dim() == 1 and a_vars.is_contiguous()
         assert b_vars.is_cuda and b_vars.dtype == torch.int64 and b_vars.shape == a_vars.shape and b_vars.is_contiguous()
         res = torch.empty_like(a_vars)
-        _chk(getattr(self._lib, fn)(self._h, a_vars.data_ptr(), b_vars.data_ptr(), a_vars.shape[0], res.data_ptr()), fn)
+        with self._hand_over():
+            _chk(getattr(self._lib, fn)(self._h, a_vars.data_ptr(), b_vars.data_ptr(), a_vars.shape[0], res.data_ptr()), fn)
         return res
 
     def conditionally_select_zero_batch(self, x_vars: torch.Tensor, select_vars: torch.Tensor) -> torch.Tensor:
@@ -246,8 +271,9 @@ class StandardComposer:
     def range_gate_batch(self, witness_vars: torch.Tensor, num_bits: int) -> None:
         """for v in witness_vars (existing Variables): range_gate(v, num_bits)"""
         assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.dim() == 1 and witness_vars.is_contiguous()
-        _chk(self._lib.pg_composer_range_gate_batch(self._h, witness_vars.data_ptr(), int(num_bits), witness_vars.shape[0]),
-             "pg_composer_range_gate_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_range_gate_batch(self._h, witness_vars.data_ptr(), int(num_bits), witness_vars.shape[0]),
+                 "pg_composer_range_gate_batch")
 
     def max_bound_ragged_batch(self, max_range: torch.Tensor, witness: torch.Tensor):
         """for i: allocate(witness[i]); max_bound(max_range[i], w) -> (result Variables, num_bits per item)"""
@@ -256,8 +282,9 @@ class StandardComposer:
         assert max_range.shape == witness.shape
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
         nb = torch.empty((witness.shape[0],), dtype=torch.int32, device=witness.device)
-        _chk(self._lib.pg_composer_max_bound_ragged_batch(self._h, max_range.data_ptr(), witness.data_ptr(), witness.shape[0],
-                                                          res.data_ptr(), nb.data_ptr()), "pg_composer_max_bound_ragged_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_max_bound_ragged_batch(self._h, max_range.data_ptr(), witness.data_ptr(), witness.shape[0],
+                                                              res.data_ptr(), nb.data_ptr()), "pg_composer_max_bound_ragged_batch")
         return res, nb
 
     def range_check_ragged_batch(self, min_range: torch.Tensor, max_range: torch.Tensor, witness: torch.Tensor):
@@ -269,9 +296,10 @@ class StandardComposer:
                              f"{witness.shape[0]}")
         res = torch.empty((witness.shape[0],), dtype=torch.int64, device=witness.device)
         nb = torch.empty((witness.shape[0],), dtype=torch.int32, device=witness.device)
-        _chk(self._lib.pg_composer_range_check_ragged_batch(self._h, min_range.data_ptr(), max_range.data_ptr(), witness.data_ptr(),
-                                                            witness.shape[0], res.data_ptr(), nb.data_ptr()),
-             "pg_composer_range_check_ragged_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_range_check_ragged_batch(self._h, min_range.data_ptr(), max_range.data_ptr(), witness.data_ptr(),
+                                                                witness.shape[0], res.data_ptr(), nb.data_ptr()),
+                 "pg_composer_range_check_ragged_batch")
         return res, nb
 
     def is_non_zero_batch(self, vars_: torch.Tensor):
@@ -280,7 +308,8 @@ class StandardComposer:
         assert vars_.is_cuda and vars_.dtype == torch.int64 and vars_.dim() == 1 and vars_.is_contiguous()
         err = torch.zeros((vars_.shape[0],), dtype=torch.uint8, device=vars_.device)
         nerr = C.c_uint64()
-        st = self._lib.pg_composer_is_non_zero_batch(self._h, vars_.data_ptr(), vars_.shape[0], err.data_ptr(), C.byref(nerr))
+        with self._hand_over():
+            st = self._lib.pg_composer_is_non_zero_batch(self._h, vars_.data_ptr(), vars_.shape[0], err.data_ptr(), C.byref(nerr))
         if st not in (0, 1):
             _chk(st, "pg_composer_is_non_zero_batch")
         return err, int(nerr.value)
@@ -292,8 +321,9 @@ class StandardComposer:
         res = torch.empty((v.shape[0], 2), dtype=torch.int64, device=v.device)
         err = torch.zeros((v.shape[0],), dtype=torch.uint8, device=v.device)
         nerr = C.c_uint64()
-        st = self._lib.pg_composer_scalar_mix_batch(self._h, v.data_ptr(), y.data_ptr(), s.data_ptr(), a.data_ptr(), b.data_ptr(),
-                                                    v.shape[0], res.data_ptr(), err.data_ptr(), C.byref(nerr))
+        with self._hand_over():
+            st = self._lib.pg_composer_scalar_mix_batch(self._h, v.data_ptr(), y.data_ptr(), s.data_ptr(), a.data_ptr(), b.data_ptr(),
+                                                        v.shape[0], res.data_ptr(), err.data_ptr(), C.byref(nerr))
         if st not in (0, 1):
             _chk(st, "pg_composer_scalar_mix_batch")
         return res, err, int(nerr.value)
@@ -306,29 +336,34 @@ class StandardComposer:
 
     def poly_gate_batch(self, a, b, c, q_m, q_l, q_r, q_o, q_c):
         n = self._vars(a, b, c)
-        _chk(self._lib.pg_composer_poly_gate_batch(self._h, a.data_ptr(), b.data_ptr(), c.data_ptr(), C.byref(q_m.c), C.byref(q_l.c),
-                                                   C.byref(q_r.c), C.byref(q_o.c), C.byref(q_c.c), n), "pg_composer_poly_gate_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_poly_gate_batch(self._h, a.data_ptr(), b.data_ptr(), c.data_ptr(), C.byref(q_m.c), C.byref(q_l.c),
+                                                       C.byref(q_r.c), C.byref(q_o.c), C.byref(q_c.c), n), "pg_composer_poly_gate_batch")
 
     def add_batch(self, q_l: BlsScalar, a, q_r: BlsScalar, b, q_c: BlsScalar) -> torch.Tensor:
         n = self._vars(a, b)
         out = torch.empty_like(a)
-        _chk(self._lib.pg_composer_add_batch(self._h, C.byref(q_l.c), a.data_ptr(), C.byref(q_r.c), b.data_ptr(), C.byref(q_c.c), n,
-                                             out.data_ptr()), "pg_composer_add_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_add_batch(self._h, C.byref(q_l.c), a.data_ptr(), C.byref(q_r.c), b.data_ptr(), C.byref(q_c.c), n,
+                                                 out.data_ptr()), "pg_composer_add_batch")
         return out
 
     def mul_batch(self, q_m: BlsScalar, a, b, q_c: BlsScalar) -> torch.Tensor:
         n = self._vars(a, b)
         out = torch.empty_like(a)
-        _chk(self._lib.pg_composer_mul_batch(self._h, C.byref(q_m.c), a.data_ptr(), b.data_ptr(), C.byref(q_c.c), n, out.data_ptr()),
-             "pg_composer_mul_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_mul_batch(self._h, C.byref(q_m.c), a.data_ptr(), b.data_ptr(), C.byref(q_c.c), n, out.data_ptr()),
+                 "pg_composer_mul_batch")
         return out
 
     def constrain_to_constant_batch(self, a, constant: BlsScalar):
-        _chk(self._lib.pg_composer_constrain_to_constant_batch(self._h, a.data_ptr(), C.byref(constant.c), self._vars(a)),
-             "pg_composer_constrain_to_constant_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_constrain_to_constant_batch(self._h, a.data_ptr(), C.byref(constant.c), self._vars(a)),
+                 "pg_composer_constrain_to_constant_batch")
 
     def boolean_gate_batch(self, a):
-        _chk(self._lib.pg_composer_boolean_gate_batch(self._h, a.data_ptr(), self._vars(a)), "pg_composer_boolean_gate_batch")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_boolean_gate_batch(self._h, a.data_ptr(), self._vars(a)), "pg_composer_boolean_gate_batch")
 
     # -- read-back ----------------------------------------------------------------------------------------
     def value(self, v: Variable) -> BlsScalar:
@@ -344,7 +379,8 @@ class StandardComposer:
 
     def construct_dense_pi_vec(self) -> torch.Tensor:
         out = torch.empty((self.circuit_size(), 4), dtype=torch.int64, device=self.engine.device)
-        _chk(self._lib.pg_composer_dense_pi(self._h, out.data_ptr()), "dense_pi")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_dense_pi(self._h, out.data_ptr()), "dense_pi")
         return out
 
     def device_columns(self) -> Columns:
@@ -369,8 +405,9 @@ class StandardComposer:
         n, nv = self.circuit_size() - gate_base, self.num_variables() - var_base
         cols = Columns.allocate(n, nv, self.engine.device, gate_base, var_base)
         cc = cols.as_c()
-        _chk(self._lib.pg_composer_copy_out(self._h, gate_base, n, var_base, nv, C.byref(cc)), "copy_out")
-        _chk(self._lib.pg_composer_sync(self._h), "sync")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_copy_out(self._h, gate_base, n, var_base, nv, C.byref(cc)), "copy_out")
+            _chk(self._lib.pg_composer_sync(self._h), "sync")
         return cols.to_numpy()
 
     def permutation_reserve(self, sparse_positions: int):
@@ -382,7 +419,8 @@ class StandardComposer:
         n = self.circuit_size()
         padded_n = padded_n or n
         out = torch.empty((4, padded_n), dtype=torch.int64, device=self.engine.device)
-        _chk(self._lib.pg_composer_permutation(self._h, padded_n, out.data_ptr()), "permutation")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_permutation(self._h, padded_n, out.data_ptr()), "permutation")
         return out
 
     def materialize(self) -> dict:
@@ -392,9 +430,13 @@ class StandardComposer:
         vals = ("w_l_value", "w_r_value", "w_o_value", "w_4_value")
         t = {k: torch.empty((n, 4), dtype=torch.int64, device=dev) for k in names + vals}
         t["w_4"] = torch.empty((n,), dtype=torch.int64, device=dev)
-        fc = _lib.FullColumnsC(**{k: v.data_ptr() for k, v in t.items()})
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self._materialize(_lib.FullColumnsC(**{k: v.data_ptr() for k, v in t.items()}))
         return t
+
+    def _materialize(self, fc: "_lib.FullColumnsC"):
+        """pg_composer_materialize into the caller's tensors, handed over to the composer's stream and back"""
+        with self._hand_over():
+            _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
 
     def wire_values(self) -> list:
         """the four wire-VALUE columns of materialize() (w_l, w_r, w_o, w_4 values: int64[circuit_size, 4] each), nothing else"""
@@ -402,7 +444,7 @@ class StandardComposer:
         vals = [torch.empty((n, 4), dtype=torch.int64, device=dev) for _ in range(4)]
         fc = _lib.FullColumnsC(w_l_value=vals[0].data_ptr(), w_r_value=vals[1].data_ptr(), w_o_value=vals[2].data_ptr(),
                                w_4_value=vals[3].data_ptr())
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self._materialize(fc)
         return vals
 
     def copy_constraints_hold(self, beta=None, gamma=None, padded_n: int | None = None) -> bool:
@@ -429,7 +471,7 @@ class StandardComposer:
         assert padded_n >= n and padded_n & (padded_n - 1) == 0, "padded_n must be a power of two >= circuit_size"
         x = torch.zeros((4, padded_n + tail, 4), dtype=torch.int64, device=self.engine.device)
         fc = _lib.FullColumnsC(w_l_value=x[0].data_ptr(), w_r_value=x[1].data_ptr(), w_o_value=x[2].data_ptr(), w_4_value=x[3].data_ptr())
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self._materialize(fc)
         self.engine.ifft(x[:, :padded_n], inplace=True)
         return x
 
@@ -453,7 +495,7 @@ class StandardComposer:
             x[i, :n] = getattr(cols, name)
         del cols
         fc = _lib.FullColumnsC(**{name: x[i].data_ptr() for i, name in enumerate(self.SELECTORS) if i >= len(Columns.SCALAR_COLS)})
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self._materialize(fc)
         self.engine.ifft(x, inplace=True)
         return {name: x[i] for i, name in enumerate(self.SELECTORS)}
 
@@ -513,11 +555,11 @@ class StandardComposer:
         dev = self.engine.device
         buf = torch.empty((n, 4), dtype=torch.int64, device=dev)
         for name in self.NON_ARITHMETIC_SELECTORS:
-            _chk(self._lib.pg_composer_materialize(self._h, C.byref(_lib.FullColumnsC(**{name: buf.data_ptr()}))), "materialize")
+            self._materialize(_lib.FullColumnsC(**{name: buf.data_ptr()}))
             if bool(buf.any()):
                 raise ValueError(f"{name} is not zero: the quotient covers the arithmetic gate, the range widget and the copy "
                                  "permutation only")
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(_lib.FullColumnsC(q_range=buf.data_ptr()))), "materialize")
+        self._materialize(_lib.FullColumnsC(q_range=buf.data_ptr()))
         q_range = None
         if bool(buf.any()):
             q_range = torch.zeros((padded_n, 4), dtype=torch.int64, device=dev)
@@ -534,7 +576,7 @@ class StandardComposer:
         wires = torch.zeros((4, padded_n + tail, 4), dtype=torch.int64, device=dev)
         fc = _lib.FullColumnsC(q_4=sel[names.index("q_4")].data_ptr(), q_arith=sel[names.index("q_arith")].data_ptr(),
                                **{f"w_{w}_value": wires[j].data_ptr() for j, w in enumerate("lro4")})
-        _chk(self._lib.pg_composer_materialize(self._h, C.byref(fc)), "materialize")
+        self._materialize(fc)
         self.engine.ifft(sel, inplace=True)
         sigma = self.permutation(padded_n)
         z = torch.zeros((padded_n + tail, 4), dtype=torch.int64, device=dev) if tail else None

@@ -77,6 +77,9 @@ struct pg_engine {
     using PlanResult = pg::PlanTotals;
     Pinned h_plan;
     PlanResult *plan() const { return h_plan.as<PlanResult>(); }
+    // behind it in the same pinned block, the bulk decoder's count of bad encodings: a word of its own, so that a decode between an
+    // asynchronous plan and pg_plan_result leaves the plan's totals alone
+    uint32_t *bad_encodings() const { return reinterpret_cast<uint32_t *>(h_plan.as<PlanResult>() + 1); }
     // scratch of the inversions: the pre-pass parks an element and its running product (64 B per element),
     // the fused mix one running product per item (32 B)
     Scratch d_prefix;
@@ -517,8 +520,9 @@ pg_status pg_engine_create(int device, pg_engine **out) {
     e->device = device;
     e->num_cus = prop.multiProcessorCount;
     if (e->d_pow2.reserve(256 * 2 * sizeof(uint4)) != PG_OK) return fail(PG_ERR_HIP, "hipMalloc(pow2 table) failed");
-    if (e->h_plan.reserve(sizeof(pg_engine::PlanResult)) != PG_OK) return fail(PG_ERR_HIP, "hipHostMalloc(plan result) failed");
+    if (e->h_plan.reserve(2 * sizeof(pg_engine::PlanResult)) != PG_OK) return fail(PG_ERR_HIP, "hipHostMalloc(plan result) failed");
     *e->plan() = pg_engine::PlanResult{0, 0, 0, 0};
+    *e->bad_encodings() = 0;
     // the pre-pass is the critical path of a call with small items: highest priority, so its waves are placed ahead of
     // the rows-only emit launch it runs beside
     int prio_lo = 0, prio_hi = 0;
@@ -561,16 +565,18 @@ pg_status pg_scalars_from_canonical_batch(pg_engine *e, const void *d_bytes, uin
     PG_TRY(check_scalars(d_out, "d_out"));
     PG_TRY(ensure_scratch(e, 1));
     hipStream_t st = static_cast<hipStream_t>(stream);
-    PG_HIP_TRY(hipSetDevice(e->device));
+    // e->d_err_count is the plan kernels' too: behind a plan still pending on another stream
+    PG_TRY(enter_stream(e, st));
+    StreamScope scope{e, st};
     uint32_t *const d_errs = e->d_err_count.as<uint32_t>();
     PG_HIP_TRY(hipMemsetAsync(d_errs, 0, sizeof(uint32_t), st));
     hipLaunchKernelGGL(pg::from_canonical_kernel, dim3((uint32_t)((batch + pg::kThreads - 1) / pg::kThreads)), dim3(pg::kThreads), 0, st,
                        static_cast<const uint4 *>(d_bytes), batch, reinterpret_cast<uint4 *>(d_out), d_bad_mask, d_errs);
     PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(&e->plan()->errs, d_errs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+    PG_HIP_TRY(hipMemcpyAsync(e->bad_encodings(), d_errs, sizeof(uint32_t), hipMemcpyDeviceToHost, st));
     PG_HIP_TRY(hipMemsetAsync(d_errs, 0, sizeof(uint32_t), st));  // zero between calls (see error_plan)
     PG_HIP_TRY(hipStreamSynchronize(st));
-    const uint32_t bad = e->plan()->errs;
+    const uint32_t bad = *e->bad_encodings();
     if (bad_count) *bad_count = bad;
     if (bad) return fail(PG_ERR_BAD_ENCODING, std::to_string(bad) + " encoding(s) are not below the modulus");
     return PG_OK;
