@@ -265,6 +265,16 @@ inline void maybe_equal(StandardComposer &c, const pg_variable *d_a, const pg_va
 inline void range_gate(StandardComposer &c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
     pg_throw(pg_composer_range_gate_batch(c.h, d_witness_var, num_bits, batch), "Batched::range_gate");
 }
+// min <= witness <= max by two such widgets on witness - min and max - witness (num_bits even, 2..252; max - min < 2^num_bits):
+// 2 (ceil(num_bits / 6) + 1) rows per item; one public pair for the batch, or device arrays with a pair per item
+inline void interval_gate(StandardComposer &c, const pg_variable *d_witness_var, const pg_scalar &min, const pg_scalar &max, uint64_t num_bits,
+                          uint64_t batch) {
+    pg_throw(pg_composer_interval_gate_batch(c.h, d_witness_var, &min, &max, num_bits, batch), "Batched::interval_gate");
+}
+inline void interval_gate(StandardComposer &c, const pg_variable *d_witness_var, const pg_scalar *d_min, const pg_scalar *d_max, uint64_t num_bits,
+                          uint64_t batch) {
+    pg_throw(pg_composer_interval_gate_ragged_batch(c.h, d_witness_var, d_min, d_max, num_bits, batch), "Batched::interval_gate (ragged)");
+}
 // Ok, or Error::NonExistingInverse when some item's value was zero (all items are appended either way, the failing
 // ones as far as the reference gets before it returns the error); *err_count = how many
 inline Result is_non_zero(StandardComposer &c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask, uint64_t *err_count) {

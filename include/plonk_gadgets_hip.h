@@ -465,6 +465,28 @@ pg_status pg_composer_maybe_equal_batch(pg_composer *c, const pg_variable *d_a_v
 pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t num_bits);
 pg_status pg_composer_range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch);
 
+/* interval_gate(witness, min, max, num_bits): min <= witness <= max for PUBLIC bounds, by two range widgets (above) on the
+ * differences d = witness - min (half h = 0) and d = max - witness (h = 1); DESIGN 3.20.  Preconditions, else
+ * PG_ERR_INVALID_ARGUMENT with nothing appended: num_bits even, 2 <= num_bits <= 252 (2^(num_bits + 1) < r: the two differences
+ * cannot add up across the modulus), and, as canonical integers, min <= max and max - min < 2^num_bits.  With k, g and pad as for
+ * range_gate an item owns 2 (g + 1) rows and 2 k new Variables; half h takes rows h (g + 1) .. and Variables first + h k ..:
+ *   first + h k + kk = c(d) >> 2 (k - 1 - kk), kk = 0 .. k - 1 (c(d) the canonical integer of d: k - 1 accumulators, then d itself)
+ *   P(p) = zero_var (p <= pad);  first + h k + (p - pad - 1) (pad < p <= 3g, so P(3g) = d)
+ *   row i < g = (P(3i), P(3i+1), P(3i+2)), q_range = 1, all five arithmetic selectors 0
+ *   row g = (d, witness, zero_var), q_range = 0, q_l = 1 and  q_r = -1, q_c = +min (h = 0: d - w + min = 0)
+ *                                                             q_r = +1, q_c = -max (h = 1: d + w - max = 0)
+ * The widget rows are, row for row, those of 2 range_gate items: q_range is written by pg_composer_materialize and their
+ * statements checked by pg_composer_check as for range_gate; the terminal rows are ordinary arithmetic rows.  A witness outside
+ * [min, max] still gets all its rows: row 0 of the half whose difference is negative fails.
+ * On EXISTING Variables, their assignments read from the composer's own table.  _batch: one host pair (min, max) for the call.
+ * _ragged_batch: device arrays with a pair per item (Montgomery form, like every pg_scalar), validated on the device before
+ * anything is appended; the error message names the first item whose pair violates a precondition. */
+pg_status pg_composer_interval_gate(pg_composer *c, pg_variable witness, const pg_scalar *min, const pg_scalar *max, uint64_t num_bits);
+pg_status pg_composer_interval_gate_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *min, const pg_scalar *max,
+                                          uint64_t num_bits, uint64_t batch);
+pg_status pg_composer_interval_gate_ragged_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *d_min,
+                                                 const pg_scalar *d_max, uint64_t num_bits, uint64_t batch);
+
 /* the composer's gate calls over device arrays of Variables, one set of selectors for the whole batch (no public
  * inputs): the loops
  *   poly_gate:             for i { composer.poly_gate(a[i], b[i], c[i], q_m, q_l, q_r, q_o, q_c, None) }

@@ -192,6 +192,9 @@ SIGNATURES = {
     "pg_composer_maybe_equal_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p]),
     "pg_composer_range_gate": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64]),
     "pg_composer_range_gate_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "pg_composer_interval_gate": (C.c_int, [C.c_void_p, C.c_uint64, _P(Scalar), _P(Scalar), C.c_uint64]),
+    "pg_composer_interval_gate_batch": (C.c_int, [C.c_void_p, C.c_void_p, _P(Scalar), _P(Scalar), C.c_uint64, C.c_uint64]),
+    "pg_composer_interval_gate_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
     "pg_composer_max_bound_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_composer_range_check_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p,
                                                        C.c_void_p]),

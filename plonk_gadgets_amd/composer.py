@@ -275,6 +275,33 @@ class StandardComposer:
             _chk(self._lib.pg_composer_range_gate_batch(self._h, witness_vars.data_ptr(), int(num_bits), witness_vars.shape[0]),
                  "pg_composer_range_gate_batch")
 
+    def interval_gate(self, witness: int, min: BlsScalar, max: BlsScalar, num_bits: int) -> None:
+        """min <= witness <= max for public bounds (num_bits even, 2..252; as integers min <= max and max - min < 2^num_bits) by two
+        range widgets on witness - min and max - witness: 2 (ceil(num_bits / 6) + 1) rows and num_bits new Variables, the
+        subtractions on the widgets' terminal rows"""
+        _chk(self._lib.pg_composer_interval_gate(self._h, int(witness), C.byref(min.c), C.byref(max.c), int(num_bits)),
+             "pg_composer_interval_gate")
+
+    def interval_gate_batch(self, witness_vars: torch.Tensor, min: BlsScalar, max: BlsScalar, num_bits: int) -> None:
+        """for v in witness_vars (existing Variables): interval_gate(v, min, max, num_bits)"""
+        assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.dim() == 1 and witness_vars.is_contiguous()
+        with self._hand_over():
+            _chk(self._lib.pg_composer_interval_gate_batch(self._h, witness_vars.data_ptr(), C.byref(min.c), C.byref(max.c), int(num_bits),
+                                                           witness_vars.shape[0]), "pg_composer_interval_gate_batch")
+
+    def interval_gate_ragged_batch(self, witness_vars: torch.Tensor, min: torch.Tensor, max: torch.Tensor, num_bits: int) -> None:
+        """for i: interval_gate(witness_vars[i], min[i], max[i], num_bits), the bounds int64[batch, 4] on the device (Montgomery form).
+        A pair that violates a precondition refuses the whole call; the error names the first such item"""
+        assert witness_vars.is_cuda and witness_vars.dtype == torch.int64 and witness_vars.dim() == 1 and witness_vars.is_contiguous()
+        for x in (min, max):
+            assert x.is_cuda and x.dtype == torch.int64 and x.dim() == 2 and x.shape[1] == 4 and x.is_contiguous()
+        if not (min.shape[0] == max.shape[0] == witness_vars.shape[0]):
+            raise ValueError(f"witness_vars, min and max differ in length: {witness_vars.shape[0]}, {min.shape[0]}, {max.shape[0]}")
+        with self._hand_over():
+            _chk(self._lib.pg_composer_interval_gate_ragged_batch(self._h, witness_vars.data_ptr(), min.data_ptr(), max.data_ptr(),
+                                                                  int(num_bits), witness_vars.shape[0]),
+                 "pg_composer_interval_gate_ragged_batch")
+
     def max_bound_ragged_batch(self, max_range: torch.Tensor, witness: torch.Tensor):
         """for i: allocate(witness[i]); max_bound(max_range[i], w) -> (result Variables, num_bits per item)"""
         for x in (max_range, witness):

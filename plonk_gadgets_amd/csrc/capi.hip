@@ -26,6 +26,7 @@
 #include "range_gate.hpp"
 #include "scalar_gadgets.hpp"
 #include "composer.hpp"
+#include "interval_gate.hpp"
 #include "permutation.hpp"
 #include "materialize.hpp"
 #include "permutation_product.hpp"
@@ -998,6 +999,41 @@ static pg_status range_gate_common(pg_engine *e, const pg_variable *d_witness_va
         if (values_only) return PG_OK;
         return launch_mode<GD, pg::EMIT_STRUCTURE>(e, A, out, batch, gate_base, var_base, zero_var, stream);
     }
+    if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+    return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+}
+
+// the interval gadget (interval_gate.hpp) on existing Variables: num_bits even, 2 .. 252, and the bounds' preconditions checked by the
+// caller.  d_min / d_max: device arrays with a pair per item, or both NULL: *min, *max for the whole call.  Every item creates
+// Variables (the two differences at least), so a refresh is never empty.
+static pg_status interval_gate_common(pg_engine *e, const pg_variable *d_witness_var, const pg_scalar *d_witness_val, const pg::Fr &min,
+                                      const pg::Fr &max, const pg_scalar *d_min, const pg_scalar *d_max, uint32_t num_bits, uint64_t batch,
+                                      uint64_t gate_base, uint64_t var_base, uint64_t zero_var, const pg_columns *out, void *stream,
+                                      bool values_only) {
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "engine is NULL");
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+    PG_TRY(check_scalars(d_witness_val, "witness value array"));
+    PG_TRY(check_columns(out));
+    if ((batch + 255) / 256 > 0xffffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "batch too large for one call");
+    pg::IntervalGateArgs A;
+    A.witness_vars = d_witness_var;
+    A.witness = reinterpret_cast<const uint4 *>(d_witness_val);
+    A.min = min;
+    A.max = max;
+    A.min_v = reinterpret_cast<const uint4 *>(d_min);
+    A.max_v = reinterpret_cast<const uint4 *>(d_max);
+    A.k = num_bits / 2;
+    A.g = (A.k + 2) / 3;
+    A.pad = 3 * A.g - A.k;
+    if (d_min) {
+        PG_TRY(check_scalars(d_min, "d_min"));
+        PG_TRY(check_scalars(d_max, "d_max"));
+        using GD = pg::IntervalGateGD<true>;
+        if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+        return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+    }
+    using GD = pg::IntervalGateGD<false>;
     if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
     return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
 }

@@ -30,7 +30,7 @@ struct pg_composer {
     Scratch perm_small, perm_big, val_ws;  // val_ws: gathered assignments of batched calls
     Scratch perm_pieces;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
     std::vector<RaggedBuffers> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
-    Pinned h_total;  // 4 words: what a call reads back (made by pg_composer_create)
+    Pinned h_total;  // 8 words: what a call reads back (made by pg_composer_create)
     uint64_t *totals() const { return h_total.as<uint64_t>(); }
     uint64_t perm_last_sparse = 0;  // size of the sparse list the last permutation needed
     uint64_t sparse_hint = 0;       // wire positions the batched calls so far are expected to put on that list
@@ -577,7 +577,7 @@ pg_status pg_composer_create(pg_engine *e, uint64_t gate_capacity, uint64_t var_
     c->stream = static_cast<hipStream_t>(stream);
     if (c->cols.create(gate_capacity, var_capacity) != PG_OK || c->d_stage.reserve(sizeof(pg::StageBlob)) != PG_OK)
         return fail(PG_ERR_HIP, "hipMalloc of the composer columns failed");
-    PG_TRY(c->h_total.reserve(32));
+    PG_TRY(c->h_total.reserve(64));
     // StandardComposer::new(): zero_var = add_witness_to_circuit_description(0), then add_dummy_constraints()
     pg_scalar zero, s;
     from_fr(pg::fr_zero(), &zero);
@@ -1156,9 +1156,136 @@ pg_status range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uin
     c->nvars += vars;
     return PG_OK;
 }
+
+// the interval gadget on existing Variables (interval_gate.hpp): min <= witness <= max by two range widgets on the differences, whose
+// terminal rows carry the subtractions.  d_min / d_max: device arrays with a pair of bounds per item, or NULL: *min, *max for the call.
+// As range_gate_batch: assignments gathered from the composer's own table, no footprint, the widget rows remembered as 2 x batch
+// range items of g + 1 rows.
+pg_status interval_num_bits(uint64_t num_bits) {
+    if (num_bits < 2 || num_bits > 252 || (num_bits & 1))
+        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: num_bits must be even and in [2, 252], got " + std::to_string(num_bits));
+    return PG_OK;
+}
+// one public pair against the preconditions, as canonical integers
+pg_status interval_bounds(const pg_scalar *min, const pg_scalar *max, uint64_t num_bits) {
+    PG_TRY(check_field(min, "min"));
+    PG_TRY(check_field(max, "max"));
+    const pg::Fr lo = pg::fr_from_mont(to_fr(min)), hi = pg::fr_from_mont(to_fr(max));
+    for (int k = 3; k >= 0; k--)
+        if (lo.l[k] != hi.l[k]) {
+            if (lo.l[k] > hi.l[k]) return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: min > max");
+            break;
+        }
+    const pg::Fr top = pg::raw_shr(pg::fr_from_mont(pg::fr_sub(to_fr(max), to_fr(min))), (uint32_t)num_bits);
+    if (top.l[0] | top.l[1] | top.l[2] | top.l[3])
+        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: max - min does not fit num_bits = " + std::to_string(num_bits) + " bits");
+    return PG_OK;
+}
+// The device arrays of the per-item form in ONE host synchronisation (the one check_var_arrays pays): the Variables' maximum and
+// digest, and, from ONE pass over the two bound arrays (interval_bounds_kernel), their digest and the items whose bounds violate the
+// preconditions.
+pg_status check_interval_arrays(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *d_min, const pg_scalar *d_max,
+                                uint64_t num_bits, uint64_t batch, pg_composer::Sig *vars_dg, pg_composer::Sig *bounds_dg) {
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    // the staging blob's last eight words: [bad items, first bad item, the bounds' digest | (unused) | check_var_arrays' three]
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 32);
+    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 64, c->stream));
+    PG_HIP_TRY(hipMemsetAsync(d_out + 1, 0xff, 8, c->stream));
+    const uint64_t most = (uint64_t)c->e->num_cus * 8, want = (batch + pg::kThreads - 1) / pg::kThreads;
+    hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, d_witness_var,
+                       batch, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
+    const uint64_t few = (uint64_t)c->e->num_cus * 2;  // (its waves end in contended atomics: interval_gate.hpp)
+    hipLaunchKernelGGL(pg::interval_bounds_kernel, dim3((uint32_t)(want < few ? want : few)), dim3(pg::kThreads), 0, c->stream,
+                       reinterpret_cast<const uint4 *>(d_min), reinterpret_cast<const uint4 *>(d_max), batch, (uint32_t)num_bits, d_out);
+    PG_HIP_TRY(hipGetLastError());
+    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint64_t *t = c->totals();
+    if (t[5] >= c->nvars)
+        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(t[5]) + " in a batched append (the composer has " +
+                                                 std::to_string(c->nvars) + ")");
+    if (t[0])
+        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: the bounds of " + std::to_string(t[0]) + " items are not reduced, have min > max or "
+                                             "max - min beyond num_bits = " + std::to_string(num_bits) + " bits; the first is item " +
+                                                 std::to_string(t[1]));
+    *vars_dg = pg_composer::Sig{t[6], t[7]};
+    *bounds_dg = pg_composer::Sig{t[2], t[3]};
+    return PG_OK;
+}
+
+pg_status interval_gate_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *min, const pg_scalar *max,
+                              const pg_scalar *d_min, const pg_scalar *d_max, uint64_t num_bits, uint64_t batch) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(interval_num_bits(num_bits));
+    const bool per_item = !min;
+    if (!per_item) PG_TRY(interval_bounds(min, max, num_bits));
+    if ((batch + 255) / 256 > 0xffffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "batch too large for one call");
+    const uint32_t k = (uint32_t)num_bits / 2, g = (k + 2) / 3;
+    const uint64_t rows = 2 * (uint64_t)(g + 1) * batch, vars = 2 * (uint64_t)k * batch;
+    PG_TRY(flush(c));
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+    pg_composer::Sig dg, bounds{0, 0};
+    pg::Fr b0 = pg::fr_zero(), b1 = pg::fr_zero();
+    if (per_item) {
+        PG_TRY(check_scalars(d_min, "d_min"));
+        PG_TRY(check_scalars(d_max, "d_max"));
+        PG_TRY(check_interval_arrays(c, d_witness_var, d_min, d_max, num_bits, batch, &dg, &bounds));
+        b0.l[0] = bounds.a;  // (the arrays' digest where the uniform call signs its two scalars)
+        b0.l[1] = bounds.b;
+    } else {
+        PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
+        b0 = to_fr(min);
+        b1 = to_fr(max);
+    }
+    PG_TRY(need(c, rows, vars));
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
+    uint4 *val = c->val_ws.as<uint4>();
+    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
+    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_witness_var, c->cols.view().vars, batch, val);
+    PG_HIP_TRY(hipGetLastError());
+    const pg_columns at = cols_at(c, c->n, c->nvars);
+    // (the rows: the Variable array, num_bits, the bounds and where the call lands)
+    SignedAppend sa(c, gadget_sig(c, per_item ? 62 : 61, b0, b1, batch, num_bits, dg), rows);
+    PG_TRY(interval_gate_common(c->e, d_witness_var, reinterpret_cast<const pg_scalar *>(val), b0, b1, per_item ? d_min : nullptr,
+                                per_item ? d_max : nullptr, (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var, &at, c->stream, sa.in_place));
+    sa.commit();
+    pg::RangeSeg *last = c->range_segs.empty() ? nullptr : &c->range_segs.back();
+    if (last && last->g == g && last->first + last->items * (g + 1) == c->n) last->items += 2 * batch;
+    else c->range_segs.push_back(pg::RangeSeg{c->n, 2 * batch, g});
+    c->n += rows;
+    c->nvars += vars;
+    return PG_OK;
+}
 }  // namespace
 
 extern "C" {
+
+pg_status pg_composer_interval_gate_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *min, const pg_scalar *max,
+                                          uint64_t num_bits, uint64_t batch) {
+    if (!min || !max) return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: min or max is NULL");
+    return interval_gate_batch(c, d_witness_var, min, max, nullptr, nullptr, num_bits, batch);
+}
+pg_status pg_composer_interval_gate_ragged_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *d_min,
+                                                 const pg_scalar *d_max, uint64_t num_bits, uint64_t batch) {
+    return interval_gate_batch(c, d_witness_var, nullptr, nullptr, d_min, d_max, num_bits, batch);
+}
+// a batch of one: the Variable goes through the composer's staging words
+pg_status pg_composer_interval_gate(pg_composer *c, pg_variable witness, const pg_scalar *min, const pg_scalar *max, uint64_t num_bits) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    if (!min || !max) return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: min or max is NULL");
+    PG_TRY(interval_num_bits(num_bits));
+    PG_TRY(interval_bounds(min, max, num_bits));
+    PG_TRY(flush(c));
+    PG_TRY(check_var(c, witness));
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    pg::StageBlob b{};
+    b.w[0] = witness;
+    PG_TRY(stage(c, b, 1));
+    return interval_gate_batch(c, c->stage_words(), min, max, nullptr, nullptr, num_bits, 1);
+}
 
 pg_status pg_composer_range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
     return range_gate_batch(c, d_witness_var, num_bits, batch);
