@@ -807,6 +807,44 @@ pg_status pg_plonk_sides_host(const uint8_t *proofs, uint64_t n, const pg_plonk_
                               const uint64_t *pi_off, const uint64_t *pi_rows, const pg_scalar *pi_vals, pg_g1_affine *bases,
                               pg_scalar *scalars, uint64_t col_stride, uint8_t *status, uint8_t *where);
 
+/* pg_plonk_range_sides: pg_plonk_sides with the range widget's term of r(X) (DESIGN sections 3.19 and 3.21;
+ * pg_composer_range_gate, pg_composer_interval_gate), for proofs of circuits that carry range_gate or interval_gate items.  The
+ * table has PG_PLONK_RANGE_SIDES_ROWS = 24 rows per proof: rows 0..22 are pg_plonk_sides' -- the same points and the same two
+ * scalars -- and
+ *       23  the key's q_range with a = 0 and b = -v rho_range,
+ *           rho_range = alpha^3 delta(b - 4a) + alpha^4 delta(c - 4b) + alpha^5 delta(a_w - 4c),  delta(f) = f (f-1)(f-2)(f-3)
+ * over the proof's evaluations a_eval, b_eval, c_eval and a_next_eval (19 more products in Fr per proof).
+ * pg_plonk_range_key: a pg_plonk_key -- its first 1392 bytes are one, field for field -- followed by the key's q_range
+ * commitment; 1488 bytes.  A record whose q_range is the identity gets row 23 = (identity, 0, 0) and with it the two sums that
+ * pg_plonk_sides gives its first 1392 bytes: keys with and without the widget can share one call.  The transcript is
+ * pg_plonk_sides': the seed has absorbed all 15 commitments of the key, q_range among them.
+ * The call writes d_bases[24 i + k], d_scalars[24 i + k] and d_scalars[col_stride + 24 i + k], the layout pg_msm_segmented
+ * takes with seg_off[s] = 24 s; a rejected proof's 24 rows are identities and zeros.  Every argument, every check, d_status
+ * and d_where as for pg_plonk_sides, with the row bounds n x 24 < 2^31 and col_stride >= 24 n; the same two launches (the
+ * second a kernel of its own) and the same 11 n bytes of device memory.  Like pg_plonk_sides the call is asynchronous: both
+ * launches are ordered on `stream` behind its earlier work, the host does not wait for them, and the engine's workspace is
+ * handed from the stream of its previous call to this one.
+ * pg_plonk_range_sides_host (host only): the same routine on the host, as pg_plonk_sides_host is pg_plonk_sides'. */
+#define PG_PLONK_RANGE_SIDES_ROWS 24
+typedef struct pg_plonk_range_key {
+    uint8_t state[200];
+    uint8_t pos, pos_begin, cur_flags, log2_n;
+    uint32_t reserved;
+    pg_scalar omega;
+    pg_g1_affine points[11]; /* as in pg_plonk_key */
+    pg_g1_affine g;
+    pg_g1_affine q_range;
+} pg_plonk_range_key;
+pg_status pg_plonk_range_sides(pg_engine *e, const uint8_t *d_proofs /* n x 1040 bytes */, uint64_t n,
+                               const pg_plonk_range_key *d_keys, uint64_t n_keys, const uint32_t *d_key_index /* [n], NULL = all 0 */,
+                               const uint64_t *d_pi_off /* [n + 1], NULL = no public inputs */, const uint64_t *d_pi_rows,
+                               const pg_scalar *d_pi_vals, pg_g1_affine *d_bases /* [24 n] */,
+                               pg_scalar *d_scalars /* [2][col_stride] */, uint64_t col_stride, uint8_t *d_status, uint8_t *d_where,
+                               void *stream);
+pg_status pg_plonk_range_sides_host(const uint8_t *proofs, uint64_t n, const pg_plonk_range_key *keys, uint64_t n_keys,
+                                    const uint32_t *key_index, const uint64_t *pi_off, const uint64_t *pi_rows, const pg_scalar *pi_vals,
+                                    pg_g1_affine *bases, pg_scalar *scalars, uint64_t col_stride, uint8_t *status, uint8_t *where);
+
 /* ---- openings: the prover's round 5 ---------------------------------------------------------------
  * Both calls take n_cols (1..32) columns p_j = d_cols[j] of n coefficients each (device, Montgomery form, 1 <= n <= 2^32) as a
  * HOST array of device pointers, which may repeat (one column can carry two weights), and n_cols host weights mu[j]; f is

@@ -73,6 +73,11 @@ class PlonkKeyC(C.Structure):
                 ("reserved", C.c_uint32), ("omega", Scalar), ("points", G1AffineC * 11), ("g", G1AffineC)]
 
 
+class PlonkRangeKeyC(C.Structure):
+    """pg_plonk_range_key: pg_plonk_key's fields, then the key's q_range commitment"""
+    _fields_ = PlonkKeyC._fields_ + [("q_range", G1AffineC)]
+
+
 # every symbol include/plonk_gadgets_hip.h declares: name -> (restype, argtypes)
 _P = C.POINTER
 SIGNATURES = {
@@ -242,6 +247,10 @@ SIGNATURES = {
                                  C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pg_plonk_sides_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                       C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "pg_plonk_range_sides": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pg_plonk_range_sides_host": (C.c_int, [C.c_void_p, C.c_uint64, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                            C.c_void_p, C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]),
     "pg_poly_open": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, _P(Scalar), C.c_void_p, C.c_void_p,
                                C.c_void_p]),
     "pg_poly_combine": (C.c_int, [C.c_void_p, _P(C.c_void_p), _P(Scalar), C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p]),

@@ -21,6 +21,11 @@
 //       22  the generator g of the opening key
 // Equal points are not merged: a point in two rows carries two scalars, and the sum is the same.  A rejected proof's rows are
 // identities and zeros -- its sums are the identity and its pairing product is 1, so the verdict is status == 0 AND check.
+//
+// With RANGE (pg_plonk_range_sides) the key record carries a twelfth point and the table a 24th row:
+//       23  the key's q_range with (0, -v rho_range), rho_range = alpha^3 delta(b - 4a) + alpha^4 delta(c - 4b) + alpha^5 delta(a_w - 4c),
+//           delta(f) = f (f-1)(f-2)(f-3): r(X)'s term of the range widget.  A record whose q_range is the identity
+//           gets (identity, 0, 0), the sums it has without the row.  Rows 0..22 are the same either way.
 #pragma once
 
 #include "g1_codec.hpp"
@@ -29,7 +34,7 @@ namespace pg {
 
 // per-proof status bytes (PG_SIDES_* of the C ABI); 1..4 are the PG_G1_* status of the first bad commitment
 constexpr uint8_t kSidesOk = 0, kSidesBadEvaluation = 5, kSidesXiInDomain = 6, kSidesBadPublicInput = 7, kSidesBadKey = 8;
-constexpr uint32_t kProofBytes = 1040, kSidesRows = 23, kSidesCommitments = 11, kSidesEvaluations = 16, kSidesEvalOffset = 528;
+constexpr uint32_t kProofBytes = 1040, kSidesRows = 23, kSidesRangeRows = 24, kSidesCommitments = 11, kSidesEvaluations = 16, kSidesEvalOffset = 528;
 constexpr uint32_t kSidesLanes = 64;  // lanes of a workgroup of plonk_sides_kernel
 // words of sponge memory per proof: the STROBE state, the 64 bytes last squeezed, beta's 32 canonical bytes
 constexpr uint32_t kSidesStateWords = 50, kSidesSqueezeAt = 50, kSidesBetaAt = 66, kSidesWords = 74;
@@ -44,6 +49,27 @@ struct PlonkKey {
     G1A g;
 };
 static_assert(sizeof(PlonkKey) == 1392, "pg_plonk_key is 1392 bytes");
+
+// pg_plonk_range_key: a PlonkKey and the commitment of the range widget's selector
+struct PlonkRangeKey {
+    PlonkKey key;
+    G1A q_range;
+};
+static_assert(sizeof(PlonkRangeKey) == 1488, "pg_plonk_range_key is 1488 bytes");
+
+// the record and the rows of a proof, without and with the range widget's row
+template <bool RANGE>
+struct SidesTable {
+    using Record = PlonkKey;
+    static constexpr uint32_t kRows = kSidesRows;
+};
+template <>
+struct SidesTable<true> {
+    using Record = PlonkRangeKey;
+    static constexpr uint32_t kRows = kSidesRangeRows;
+};
+PG_HD const PlonkKey *sides_key_of(const PlonkKey *rec) { return rec; }
+PG_HD const PlonkKey *sides_key_of(const PlonkRangeKey *rec) { return &rec->key; }
 
 // ---- Keccak-f[1600] -------------------------------------------------------------------------------------------------------------
 PG_HD uint64_t rol64(uint64_t v, int s) { return s ? (v << s) | (v >> (64 - s)) : v; }
@@ -278,21 +304,34 @@ PG_HD Fr sides_omega_pow(const Fr &omega, uint64_t row, uint32_t m) {
     return acc;
 }
 
+// the range widget's delta(f) = f (f - 1)(f - 2)(f - 3), and 4 f
+PG_HD Fr sides_delta(const Fr &f) {
+    const Fr one = fr_one(), f1 = fr_sub(f, one), f2 = fr_sub(f1, one), f3 = fr_sub(f2, one);
+    return fr_mul(fr_mul(f, f1), fr_mul(f2, f3));
+}
+PG_HD Fr sides_times4(const Fr &f) {
+    const Fr f2 = fr_add(f, f);
+    return fr_add(f2, f2);
+}
+
 // One proof.  cstat: the g1_decode status of its 11 commitments, whose points already stand in bases[0..10]; pi_rows / pi_vals
 // [pi_begin, pi_end) its public inputs (Montgomery form); mem: kSidesWords words, S apart.  Writes the 23 bases, the 23 + 23
-// scalars, *status and *where.  The tests are made in the order key, commitments, evaluations, public inputs, xi^n: the first
-// that fails is the one reported.
-template <int S>
-PG_HD void plonk_sides_one(const uint8_t *proof, const PlonkKey *keys, uint64_t n_keys, uint32_t key_index, const uint64_t *pi_rows,
+// scalars (24 with RANGE), *status and *where.  The tests are made in the order key, commitments, evaluations, public inputs, xi^n:
+// the first that fails is the one reported.
+template <int S, bool RANGE>
+PG_HD void plonk_sides_one(const uint8_t *proof, const typename SidesTable<RANGE>::Record *keys, uint64_t n_keys, uint32_t key_index, const uint64_t *pi_rows,
                            const Fr *pi_vals, uint64_t pi_begin, uint64_t pi_end, const uint8_t *cstat, uint32_t *mem, G1A *bases,
                            Fr *sa, Fr *sb, uint8_t *status, uint8_t *where) {
+    constexpr uint32_t kRows = SidesTable<RANGE>::kRows;
     uint8_t st = kSidesOk, wh = 0;
-    const PlonkKey *key = keys;
+    const typename SidesTable<RANGE>::Record *rec = keys;
+    const PlonkKey *key = sides_key_of(rec);
     uint32_t m = 0;
     if (key_index >= n_keys) {
         st = kSidesBadKey;
     } else {
-        key = keys + key_index;
+        rec = keys + key_index;
+        key = sides_key_of(rec);
         m = key->log2_n;
         if (m > 32 || key->pos >= kStrobeR || key->pos_begin > kStrobeR) st = kSidesBadKey;
     }
@@ -333,7 +372,7 @@ PG_HD void plonk_sides_one(const uint8_t *proof, const PlonkKey *keys, uint64_t 
     *where = wh;
     if (st != kSidesOk) {
 #pragma unroll 1
-        for (uint32_t row = 0; row < kSidesRows; row++) {
+        for (uint32_t row = 0; row < kRows; row++) {
             bases[row] = g1a_identity();
             sa[row] = fr_zero();
             sb[row] = fr_zero();
@@ -383,7 +422,7 @@ PG_HD void plonk_sides_one(const uint8_t *proof, const PlonkKey *keys, uint64_t 
     for (uint32_t k = 0; k < 11; k++) bases[11 + k] = key->points[k];
     bases[22] = key->g;
 #pragma unroll 1
-    for (uint32_t row = 0; row < kSidesRows; row++) sa[row] = fr_zero();
+    for (uint32_t row = 0; row < kRows; row++) sa[row] = fr_zero();
     sa[9] = one;
     sa[10] = u;
 
@@ -443,34 +482,68 @@ PG_HD void plonk_sides_one(const uint8_t *proof, const PlonkKey *keys, uint64_t 
     sb[14] = fr_neg(fr_mul(vqa, c));
     sb[15] = fr_neg(fr_mul(vqa, d));
     sb[21] = fr_mul(fr_mul(v, beta), ap3zw);
+    if constexpr (RANGE) {
+        // row 23, last: everything above is stored, and the four evaluations are read again rather than kept
+        const G1A q = rec->q_range;
+        bases[23] = q;
+        Fr rho = fr_zero();
+        if (!g1a_is_identity(q)) {
+            const Fr ra = sides_eval(proof, kEvA), rb = sides_eval(proof, kEvB), rc = sides_eval(proof, kEvC);
+            // alpha^3 (delta(b - 4a) + alpha (delta(c - 4b) + alpha delta(a_w - 4c)))
+            rho = sides_delta(fr_sub(sides_eval(proof, kEvANext), sides_times4(rc)));
+            rho = fr_add(fr_mul(rho, alpha), sides_delta(fr_sub(rc, sides_times4(rb))));
+            rho = fr_add(fr_mul(rho, alpha), sides_delta(fr_sub(rb, sides_times4(ra))));
+            rho = fr_mul(rho, fr_mul(fr_square(alpha), alpha));
+        }
+        sb[23] = fr_neg(fr_mul(v, rho));
+    }
 }
 
 #if defined(__HIPCC__)
 // One lane per commitment, commitment j of proof i at proofs + 1040 i + 48 j (16-byte aligned when proofs is): the point to
-// bases[23 i + j], the status to cstat[11 i + j].  Nothing waits on another lane.
-__global__ __launch_bounds__(kThreads) void plonk_sides_decode_kernel(const uint8_t *proofs, uint64_t n, G1A *bases, uint8_t *cstat) {
+// bases[rows i + j], rows the table's rows per proof (23 or 24), the status to cstat[11 i + j].  Nothing waits on another lane.
+__global__ __launch_bounds__(kThreads) void plonk_sides_decode_kernel(const uint8_t *proofs, uint64_t n, uint32_t rows, G1A *bases,
+                                                                      uint8_t *cstat) {
     const uint64_t total = n * kSidesCommitments;
     for (uint64_t t = (uint64_t)blockIdx.x * kThreads + threadIdx.x; t < total; t += (uint64_t)gridDim.x * kThreads) {
         const uint64_t i = t / kSidesCommitments, j = t % kSidesCommitments;
         G1A p;
         const uint8_t st = g1_decode(g1_load_bytes(reinterpret_cast<const uint4 *>(proofs + i * kProofBytes + 48 * j), 0), true, &p);
-        bases[i * kSidesRows + j] = p;
+        bases[i * rows + j] = p;
         cstat[t] = st;
     }
 }
 
 // One lane per proof, 64 lanes a workgroup; the sponge memory of lane l is the words lds[i * 64 + l].
-__global__ __launch_bounds__(kSidesLanes) void plonk_sides_kernel(const uint8_t *proofs, uint64_t n, const PlonkKey *keys, uint64_t n_keys,
-                                                                  const uint32_t *key_index, const uint64_t *pi_off, const uint64_t *pi_rows,
-                                                                  const Fr *pi_vals, const uint8_t *cstat, G1A *bases, Fr *scalars,
-                                                                  uint64_t col_stride, uint8_t *status, uint8_t *where) {
+template <bool RANGE>
+__device__ __forceinline__ void plonk_sides_lane(const uint8_t *proofs, uint64_t n, const typename SidesTable<RANGE>::Record *keys,
+                                                 uint64_t n_keys, const uint32_t *key_index, const uint64_t *pi_off, const uint64_t *pi_rows,
+                                                 const Fr *pi_vals, const uint8_t *cstat, G1A *bases, Fr *scalars, uint64_t col_stride,
+                                                 uint8_t *status, uint8_t *where) {
+    constexpr uint32_t kRows = SidesTable<RANGE>::kRows;
     __shared__ uint32_t lds[kSidesWords * kSidesLanes];
     const uint64_t i = (uint64_t)blockIdx.x * kSidesLanes + threadIdx.x;
     if (i >= n) return;
     const uint64_t lo = pi_off ? pi_off[i] : 0, hi = pi_off ? pi_off[i + 1] : 0;
-    plonk_sides_one<(int)kSidesLanes>(proofs + i * kProofBytes, keys, n_keys, key_index ? key_index[i] : 0u, pi_rows, pi_vals, lo, hi,
-                                      cstat + i * kSidesCommitments, lds + threadIdx.x, bases + i * kSidesRows, scalars + i * kSidesRows,
-                                      scalars + col_stride + i * kSidesRows, status + i, where + i);
+    plonk_sides_one<(int)kSidesLanes, RANGE>(proofs + i * kProofBytes, keys, n_keys, key_index ? key_index[i] : 0u, pi_rows, pi_vals, lo, hi,
+                                             cstat + i * kSidesCommitments, lds + threadIdx.x, bases + i * kRows, scalars + i * kRows,
+                                             scalars + col_stride + i * kRows, status + i, where + i);
+}
+
+__global__ __launch_bounds__(kSidesLanes) void plonk_sides_kernel(const uint8_t *proofs, uint64_t n, const PlonkKey *keys, uint64_t n_keys,
+                                                                  const uint32_t *key_index, const uint64_t *pi_off, const uint64_t *pi_rows,
+                                                                  const Fr *pi_vals, const uint8_t *cstat, G1A *bases, Fr *scalars,
+                                                                  uint64_t col_stride, uint8_t *status, uint8_t *where) {
+    plonk_sides_lane<false>(proofs, n, keys, n_keys, key_index, pi_off, pi_rows, pi_vals, cstat, bases, scalars, col_stride, status, where);
+}
+
+// ... with the range widget's row: records of 1488 bytes, 24 rows a proof
+__global__ __launch_bounds__(kSidesLanes) void plonk_range_sides_kernel(const uint8_t *proofs, uint64_t n, const PlonkRangeKey *keys,
+                                                                        uint64_t n_keys, const uint32_t *key_index, const uint64_t *pi_off,
+                                                                        const uint64_t *pi_rows, const Fr *pi_vals, const uint8_t *cstat,
+                                                                        G1A *bases, Fr *scalars, uint64_t col_stride, uint8_t *status,
+                                                                        uint8_t *where) {
+    plonk_sides_lane<true>(proofs, n, keys, n_keys, key_index, pi_off, pi_rows, pi_vals, cstat, bases, scalars, col_stride, status, where);
 }
 #endif
 

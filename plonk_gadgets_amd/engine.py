@@ -830,22 +830,27 @@ class Engine:
     # ---- the verifier's sides from proof bytes (pg_plonk_sides) ------------------------------------------------------
     def plonk_sides(self, proofs: torch.Tensor, keys: torch.Tensor, key_index: torch.Tensor | None = None,
                     pi_off: torch.Tensor | None = None, pi_rows: torch.Tensor | None = None, pi_vals: torch.Tensor | None = None,
-                    col_stride: int | None = None):
+                    col_stride: int | None = None, range_term: bool = False):
         """pg_plonk_sides, everything on the device: proofs uint8[n, 1040] (or flat), keys uint8[n_keys * 1392] (the records of
         VerifierKey.record back to back), key_index int32[n] or None (key 0 for all), the public inputs as CSR arrays pi_off
         int64[n + 1], pi_rows int64[k], pi_vals int64[k, 4] (Montgomery limbs) or None for none -> (bases int64[23 n, 12],
         scalars int64[2, col_stride, 4], status uint8[n], where uint8[n]): what msm_segmented takes with the offsets 23 i.  The
-        verdict on proof i is status[i] == 0 AND its pairing check (a rejected proof's rows are identities and zeros)."""
-        from .verifier import PROOF_BYTES, SIDES_ROWS, VerifierKey
+        verdict on proof i is status[i] == 0 AND its pairing check (a rejected proof's rows are identities and zeros).
+        range_term: pg_plonk_range_sides -- keys uint8[n_keys * 1488], the records of VerifierKey.record(...,
+        range_term=True), and 24 rows a proof, the last one the key's q_range with the range widget's coefficient: bases
+        int64[24 n, 12], the offsets 24 i."""
+        from .verifier import PROOF_BYTES, RANGE_SIDES_ROWS, SIDES_ROWS, VerifierKey
+        record_size = VerifierKey.RANGE_RECORD_SIZE if range_term else VerifierKey.RECORD_SIZE
+        name = "pg_plonk_range_sides" if range_term else "pg_plonk_sides"
 
         def ok(t, dtype, what):
             if not (isinstance(t, torch.Tensor) and t.dtype == dtype and t.device == self.device and t.is_contiguous()):
                 raise ValueError(f"{what} must be a contiguous {dtype} tensor on the engine's device")
         ok(proofs, torch.uint8, "proofs")
         ok(keys, torch.uint8, "keys")
-        if proofs.numel() % PROOF_BYTES or keys.numel() % VerifierKey.RECORD_SIZE:
-            raise ValueError(f"proofs are {PROOF_BYTES} bytes each and key records {VerifierKey.RECORD_SIZE}")
-        n, n_keys = proofs.numel() // PROOF_BYTES, keys.numel() // VerifierKey.RECORD_SIZE
+        if proofs.numel() % PROOF_BYTES or keys.numel() % record_size:
+            raise ValueError(f"proofs are {PROOF_BYTES} bytes each and key records {record_size}")
+        n, n_keys = proofs.numel() // PROOF_BYTES, keys.numel() // record_size
         if key_index is not None:
             ok(key_index, torch.int32, "key_index")
             if key_index.numel() != n:
@@ -858,18 +863,18 @@ class Engine:
             ok(pi_vals, torch.int64, "pi_vals")
             if pi_off.numel() != n + 1 or pi_vals.numel() != 4 * pi_rows.numel():
                 raise ValueError("pi_off holds n + 1 offsets, pi_vals four limbs per row of pi_rows")
-        rows = SIDES_ROWS * n
+        rows = (RANGE_SIDES_ROWS if range_term else SIDES_ROWS) * n
         col_stride = rows if col_stride is None else int(col_stride)
         bases = torch.empty((rows, 12), dtype=torch.int64, device=self.device)
         scalars = torch.empty((2, col_stride, 4), dtype=torch.int64, device=self.device)
         status = torch.empty((n,), dtype=torch.uint8, device=self.device)
         where = torch.empty((n,), dtype=torch.uint8, device=self.device)
         ptr = lambda t: t.data_ptr() if t is not None else None
-        st = self._lib.pg_plonk_sides(self._h, proofs.data_ptr(), n, keys.data_ptr(), n_keys, ptr(key_index), ptr(pi_off), ptr(pi_rows),
+        st = getattr(self._lib, name)(self._h, proofs.data_ptr(), n, keys.data_ptr(), n_keys, ptr(key_index), ptr(pi_off), ptr(pi_rows),
                                       ptr(pi_vals), bases.data_ptr(), scalars.data_ptr(), col_stride, status.data_ptr(),
                                       where.data_ptr(), self._stream())
         if st != 0:
-            raise PgError(st, "pg_plonk_sides")
+            raise PgError(st, name)
         return bases, scalars, status, where
 
     # ---- two-step forms of the ragged batches (plan once into caller-owned buffers, emit many times) ------------

@@ -22,7 +22,9 @@ be deterministic.  verify_each sums every proof's two sides in ONE pg_msm_segmen
 
 verify_encoded is verify_each for proofs given as bytes with the host out of the loop: pg_plonk_sides decodes
 the commitments, replays the transcript from a per-key seed (VerifierKey.record) and writes every proof's fixed table of 23 rows on
-the device, which the same segmented MSM and pairing check consume; `sides` above is the model it is tested against."""
+the device, which the same segmented MSM and pairing check consume; `sides` above is the model it is tested against.  With
+range_term=True it goes through pg_plonk_range_sides: a 24th row, rho_range [q_range], for proofs of circuits
+with range_gate or interval_gate items."""
 from __future__ import annotations
 
 import ctypes as C
@@ -44,6 +46,7 @@ MAX_PAIRS = 8
 # pg_plonk_sides: a proof's bytes, the rows of its table, the key commitments of rows 11..21 in their order
 PROOF_BYTES = Proof.SIZE
 SIDES_ROWS = 23
+RANGE_SIDES_ROWS = 24  # pg_plonk_range_sides: row 23 is the key's q_range
 SIDES_KEY_ROWS = ("q_m", "q_l", "q_r", "q_o", "q_4", "q_c", "q_arith", "left_sigma", "right_sigma", "out_sigma", "fourth_sigma")
 SIDES_STATUS = ("PG_SIDES_OK", "PG_G1_BAD_ENCODING", "PG_G1_NOT_ON_CURVE", "PG_G1_NOT_IN_SUBGROUP", "PG_G1_NOT_REDUCED",
                 "PG_SIDES_BAD_EVALUATION", "PG_SIDES_XI_IN_DOMAIN", "PG_SIDES_BAD_PUBLIC_INPUT", "PG_SIDES_BAD_KEY")
@@ -135,6 +138,7 @@ class VerifierKey:
     NAMES = SELECTORS + SIGMAS
     SIZE = 8 + 48 * len(NAMES)
     RECORD_SIZE = C.sizeof(_lib.PlonkKeyC)
+    RANGE_RECORD_SIZE = C.sizeof(_lib.PlonkRangeKeyC)
 
     def __init__(self, n: int, commitments: dict):
         if n < 1 or n & (n - 1):
@@ -147,10 +151,11 @@ class VerifierKey:
         self.valid = all(g1_in_subgroup(c) for c in self.commitments.values())
         self._seeds = {}
 
-    def record(self, ok, label=b"plonk") -> bytes:
+    def record(self, ok, label=b"plonk", range_term: bool = False) -> bytes:
         """the bytes of one pg_plonk_key for this key, the generator of the opening key `ok` and the transcript label: the
         STROBE state after the label, circuit_domain_sep(n) and the 15 commitments (computed once per label and kept), log2 n,
-        omega, the 11 key points of the sides table, ok.g"""
+        omega, the 11 key points of the sides table, ok.g.  With range_term the 1488 bytes of a pg_plonk_range_key: the same
+        record followed by the key's q_range commitment."""
         label = bytes(label)
         seed = self._seeds.get(label)
         if seed is None:
@@ -160,7 +165,9 @@ class VerifierKey:
                 tr.append_commitment(name.encode(), self.commitments[name])
             st = tr.strobe
             seed = self._seeds[label] = (bytes(st.state), st.pos, st.pos_begin, st.cur_flags)
-        rec = _lib.PlonkKeyC()
+        rec = _lib.PlonkRangeKeyC() if range_term else _lib.PlonkKeyC()
+        if range_term:
+            rec.q_range = self.commitments["q_range"].c
         C.memmove(rec.state, seed[0], 200)
         rec.pos, rec.pos_begin, rec.cur_flags = seed[1:]
         rec.log2_n = self.n.bit_length() - 1
@@ -386,7 +393,7 @@ def _proof_bytes(proofs):
     return len(data) // PROOF_BYTES, data
 
 
-def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_status=False):
+def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_status=False, range_term: bool = False):
     """verify_each for a batch given as BYTES, the sides built on the device (pg_plonk_sides).
     proofs: a bytes-like of n x 1040, a uint8[n, 1040] tensor on the host or the device, or a list of Proof (taken by their
     to_bytes).  vks / public_inputs / label: one per proof, or one for all.  One upload of the inputs (proofs, the records of
@@ -397,22 +404,27 @@ def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_s
     The answer is verify's, proof by proof, with one exception: a public-input row >= n.  sides / verify take omega^row for
     any row (row n is row 0 to them) and may accept; here such a proof is rejected with PG_SIDES_BAD_PUBLIC_INPUT.
     With return_status also the lists (status, where) of pg_plonk_sides (SIDES_STATUS names the values; a key that is not
-    valid gives PG_SIDES_BAD_KEY).  ValueError also for a key whose q_range commitment is not the identity: pg_plonk_key has 11
-    points and the table 23 rows, none of them for the range widget's term."""
+    valid gives PG_SIDES_BAD_KEY).
+    range_term: the whole batch goes through pg_plonk_range_sides: records of 1488 bytes, 24 rows a proof
+    -- row 23 is rho_range [q_range], the range widget's term, what verify asks of `sides` -- and the offsets 24 i.  Keys with
+    and without range_gate / interval_gate items can share such a call: an identity q_range gives an empty row.  Without it (the
+    default) ValueError also for a key whose q_range commitment is not the identity: pg_plonk_key has 11 points and its table 23
+    rows, none of them for that term."""
     engine = ok.engine
     n, data = _proof_bytes(proofs)
     if n == 0:
         return ([], [], []) if return_status else []
     vks, pis, labels = _broadcast(vks, n), _broadcast(public_inputs, n), _broadcast(label, n)
-    if any(not vk.commitments["q_range"].is_identity() for vk in vks):
-        raise ValueError("a key with a live q_range (range_gate items): pg_plonk_sides builds no row for the range term; "
-                         "use verify_each")
+    if not range_term and any(not vk.commitments["q_range"].is_identity() for vk in vks):
+        raise ValueError("a key with a live q_range (range_gate or interval_gate items): pg_plonk_sides builds no row for the range "
+                         "term; pass range_term=True, or use verify_each")
+    rows = RANGE_SIDES_ROWS if range_term else SIDES_ROWS
     table, records, key_index, bad_key = {}, [], [], []
     for i in range(n):
         k = (id(vks[i]), bytes(labels[i]))
         if k not in table:
             table[k] = len(records)
-            records.append(vks[i].record(ok, k[1]))
+            records.append(vks[i].record(ok, k[1], range_term))
         key_index.append(table[k])
         if not vks[i].valid:
             bad_key.append(i)
@@ -457,8 +469,9 @@ def verify_encoded(proofs, vks, ok, public_inputs=None, label=b"plonk", return_s
         d_proofs = d_proofs.clone()
     vals = view("vals", torch.int64)
     bases, scalars, status, where = engine.plonk_sides(d_proofs, view("keys"), view("index", torch.int32), view("off", torch.int64),
-                                                       view("rows", torch.int64), vals.view(-1, 4) if vals is not None else None)
-    sums = engine.msm_segmented(bases, scalars, range(0, SIDES_ROWS * n + 1, SIDES_ROWS))
+                                                       view("rows", torch.int64), vals.view(-1, 4) if vals is not None else None,
+                                                       range_term=range_term)
+    sums = engine.msm_segmented(bases, scalars, range(0, rows * n + 1, rows))
     good = pairing_check(engine, sums, [ok.prepared_tau_h, ok.prepared_h])
     verdict = ((status == 0) & (good != 0)).to(torch.uint8)
     verdict, status, where = torch.stack([verdict, status, where]).cpu().tolist()
