@@ -992,9 +992,8 @@ static pg_status range_gate_common(pg_engine *e, const pg_variable *d_witness_va
     pg::RangeGateArgs A;
     A.witness_vars = d_witness_var;
     A.witness = reinterpret_cast<const uint4 *>(d_witness_val);
-    A.k = num_bits / 2;
-    A.g = (A.k + 2) / 3;
-    A.pad = 3 * A.g - A.k;
+    const pg::WidgetShape shape = pg::widget_shape(num_bits);
+    A.k = shape.k; A.g = shape.g; A.pad = shape.pad;
     if (A.k == 1) {
         if (values_only) return PG_OK;
         return launch_mode<GD, pg::EMIT_STRUCTURE>(e, A, out, batch, gate_base, var_base, zero_var, stream);
@@ -1023,9 +1022,8 @@ static pg_status interval_gate_common(pg_engine *e, const pg_variable *d_witness
     A.max = max;
     A.min_v = reinterpret_cast<const uint4 *>(d_min);
     A.max_v = reinterpret_cast<const uint4 *>(d_max);
-    A.k = num_bits / 2;
-    A.g = (A.k + 2) / 3;
-    A.pad = 3 * A.g - A.k;
+    const pg::WidgetShape shape = pg::widget_shape(num_bits);
+    A.k = shape.k; A.g = shape.g; A.pad = shape.pad;
     if (d_min) {
         PG_TRY(check_scalars(d_min, "d_min"));
         PG_TRY(check_scalars(d_max, "d_max"));

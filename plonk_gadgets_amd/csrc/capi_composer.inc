@@ -141,11 +141,38 @@ struct SignedAppend {
         if (!settled && active) end_refresh();
     }
 };
+// Which call an append's signature is for: the first word that gadget_sig and gate_batch hash.  Two calls never share one: a different
+// append at the same place must not be taken for rows already in place, whatever its other words are.
+// run_gate's signature (a single gate call) starts with cmd.op instead -- OP_ADD_INPUT .. OP_MUL = 0 .. 3 (composer.hpp), which
+// RANGE_CHECK and MAX_BOUND meet in value.  That is no shared kind: run_gate hashes 240 bytes (six words, six scalars) where gadget_sig
+// hashes 128 and gate_batch 232, and strings of different lengths agree only where the 128-bit hash itself collides -- the chance any
+// two different appends take.
+enum class SigKind : uint64_t {
+    RANGE_CHECK = 1,                 // pg_range_check (= Queued::kind)
+    MAX_BOUND = 2,                   // pg_max_bound (= Queued::kind)
+    RANGE_CHECK_BATCH = 11,          // pg_composer_range_check_batch
+    MAX_BOUND_BATCH = 12,            // pg_composer_max_bound_batch
+    SCALAR_MIX_BATCH = 13,           // pg_composer_scalar_mix_batch
+    RANGE_CHECK_ALLOCATED_BATCH = 21,  // pg_composer_range_check_allocated_batch
+    MAX_BOUND_ALLOCATED_BATCH = 22,  // pg_composer_max_bound_allocated_batch
+    DECOMPOSITION_BATCH = 23,        // pg_composer_scalar_decomposition_batch
+    SELECT_ZERO_BATCH = 24,          // pg_composer_conditionally_select_zero_batch
+    SELECT_ONE_BATCH = 25,           // pg_composer_conditionally_select_one_batch
+    MAYBE_EQUAL_BATCH = 26,          // pg_composer_maybe_equal_batch
+    RANGE_GATE_BATCH = 27,           // pg_composer_range_gate_batch, pg_composer_range_gate (a batch of one)
+    IS_NON_ZERO_BATCH = 28,          // pg_composer_is_non_zero_batch
+    GATE_BATCH = 29,                 // the gate batches (gate_batch: poly_gate, add, mul, constrain_to_constant, boolean_gate)
+    RANGE_CHECK_RAGGED_BATCH = 30,   // pg_composer_range_check_ragged_batch
+    MAX_BOUND_RAGGED_BATCH = 31,     // pg_composer_max_bound_ragged_batch (it signed with 27, range_gate's, until the kinds had names)
+    DECOMPOSITION = 43,              // pg_scalar_decomposition_gadget
+    INTERVAL_GATE_BATCH = 61,        // pg_composer_interval_gate_batch, pg_composer_interval_gate (a batch of one)
+    INTERVAL_GATE_RAGGED_BATCH = 62  // pg_composer_interval_gate_ragged_batch
+};
 // kind: which call; b0, b1: its public scalars; extra: a public integer; dg: the digest of the device arrays its rows depend on
-pg_composer::Sig gadget_sig(const pg_composer *c, uint64_t kind, const pg::Fr &b0, const pg::Fr &b1, uint64_t batch, uint64_t extra,
+pg_composer::Sig gadget_sig(const pg_composer *c, SigKind kind, const pg::Fr &b0, const pg::Fr &b1, uint64_t batch, uint64_t extra,
                             const pg_composer::Sig &dg = pg_composer::Sig{0, 0}) {
     SigHasher h;
-    h.u64(kind); h.fr(b0); h.fr(b1); h.u64(batch); h.u64(extra); h.u64(dg.a); h.u64(dg.b);
+    h.u64((uint64_t)kind); h.fr(b0); h.fr(b1); h.u64(batch); h.u64(extra); h.u64(dg.a); h.u64(dg.b);
     h.u64(c->n); h.u64(c->nvars); h.u64(c->zero_var);
     return h.done();
 }
@@ -182,6 +209,11 @@ pg_status check_var(const pg_composer *c, pg_variable v) {
     return PG_OK;
 }
 
+// one pass over n words of a device array on the composer's stream: their maximum into out[0], their salted digest into out[1], out[2]
+void digest_words(pg_composer *c, const uint64_t *d, uint64_t n, unsigned long long *d_out, unsigned long long salt) {
+    const uint64_t want = (n + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
+    hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, d, n, d_out, salt);
+}
 // device arrays of Variables handed to a batched append: every entry must be a Variable of this composer.  One small
 // reduction per array on the composer's stream and one host synchronisation; nothing has been appended when it fails.
 // The same pass digests the arrays (128 bits over values and positions, the arrays salted by their place in the list):
@@ -193,13 +225,10 @@ pg_status check_var_arrays(pg_composer *c, std::initializer_list<const pg_variab
     PG_HIP_TRY(hipSetDevice(c->e->device));
     unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);  // the staging blob's last three words
     PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
-    const uint64_t want = (batch + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
     unsigned long long salt = 0x243f6a8885a308d3ull;
     for (const pg_variable *a : arrays) {
         salt += 0x9e3779b97f4a7c15ull;
-        if (!a) continue;
-        hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, a, batch,
-                           d_out, salt);
+        if (a) digest_words(c, a, batch, d_out, salt);
     }
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
@@ -218,12 +247,8 @@ pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_comp
     PG_HIP_TRY(hipSetDevice(c->e->device));
     unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);
     PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
-    const uint64_t words = 4 * n, want = (words + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
-    hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream,
-                       reinterpret_cast<const uint64_t *>(d), words, d_out, 0x13198a2e03707344ull);
-    if (d2)
-        hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream,
-                           reinterpret_cast<const uint64_t *>(d2), words, d_out, 0x13198a2e03707344ull + 0x9e3779b97f4a7c15ull);
+    digest_words(c, reinterpret_cast<const uint64_t *>(d), 4 * n, d_out, 0x13198a2e03707344ull);
+    if (d2) digest_words(c, reinterpret_cast<const uint64_t *>(d2), 4 * n, d_out, 0x13198a2e03707344ull + 0x9e3779b97f4a7c15ull);
     PG_HIP_TRY(hipGetLastError());
     PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
     PG_HIP_TRY(hipStreamSynchronize(c->stream));
@@ -800,32 +825,37 @@ pg_status pg_allocated_scalar_allocate(pg_composer *c, const pg_scalar *scalar, 
     return PG_OK;
 }
 
-pg_status pg_range_check(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
-                         const pg_allocated_scalar *witness, pg_variable *out) {
-    if (!c || !witness || !out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!min_range || !max_range) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!(c->last_kind == 1 && std::memcmp(&c->last_min, min_range, 32) == 0 && std::memcmp(&c->last_max, max_range, 32) == 0)) {
+// The two ladder gadgets called one at a time on an allocated witness: recorded on the queue (flushed together with their neighbours:
+// consecutive calls with the same bounds are one launch) or launched as a batch of one.  kind: the call's SigKind, Queued::kind and
+// pg_composer::last_kind in one; min_range: NULL for max_bound (zero wherever the call's pair of bounds is kept).
+static pg_status single_ladder(pg_composer *c, SigKind kind, const pg_scalar *min_range, const pg_scalar *max_range,
+                               const pg_allocated_scalar *witness, pg_variable *out, uint64_t *num_bits) {
+    const bool range_check = kind == SigKind::RANGE_CHECK;
+    if (!c || !witness || !out || !max_range || (range_check && !min_range)) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    const pg_scalar mn = range_check ? *min_range : pg_scalar{};
+    if (!(c->last_kind == (int)kind && std::memcmp(&c->last_min, &mn, 32) == 0 && std::memcmp(&c->last_max, max_range, 32) == 0)) {
         c->last_kind = 0;
-        PG_TRY(pg_range_check_layout(min_range, max_range, 1, &c->last_lay));
-        c->last_min = *min_range;
+        PG_TRY(range_check ? pg_range_check_layout(&mn, max_range, 1, &c->last_lay) : pg_max_bound_layout(max_range, 1, &c->last_lay));
+        c->last_min = mn;
         c->last_max = *max_range;
-        c->last_kind = 1;
+        c->last_kind = (int)kind;
     }
     const pg_layout lay = c->last_lay;
-    const uint64_t rows = lay.gates_per_item, vars = pg::kind_vars(pg::WIRES_RANGE_CHECK_ALLOCATED, lay.num_bits);  // the witness is already allocated
+    // (the witness is already allocated: the `_allocated` twin's Variables)
+    const uint64_t rows = lay.gates_per_item, vars = pg::kind_vars(pg::ladder_kind((uint32_t)kind, false), lay.num_bits);
     PG_TRY(need(c, rows, vars));
     PG_TRY(check_var(c, witness->var));
     if (!is_reduced(to_fr(&witness->scalar))) return fail(PG_ERR_INVALID_ARGUMENT, "witness is not a reduced BlsScalar");
-    if (lay.num_bits < 2 || lay.num_bits > 255) return fail(PG_ERR_INVALID_ARGUMENT, "ladder length out of range");
+    if (range_check && (lay.num_bits < 2 || lay.num_bits > 255)) return fail(PG_ERR_INVALID_ARGUMENT, "ladder length out of range");
     // the rows: a function of the bounds, the witness VARIABLE and where the call lands
     if (c->queueing && c->queue.size() >= PG_QUEUE_MAX) PG_TRY(flush(c));  // (before the decision: a flush can fail)
-    SignedAppend sa(c, gadget_sig(c, 1, to_fr(min_range), to_fr(max_range), 1, witness->var), rows);
-    if (c->queueing) {  // recorded; flushed together with its neighbours (consecutive calls with the same bounds: one launch)
+    SignedAppend sa(c, gadget_sig(c, kind, to_fr(&mn), to_fr(max_range), 1, witness->var), rows);
+    if (c->queueing) {
         c->queue.emplace_back();
         pg_composer::Queued &q = c->queue.back();
         q.in_place = sa.in_place;
-        q.kind = 1;
-        q.b0 = to_fr(min_range);
+        q.kind = (uint8_t)kind;
+        q.b0 = to_fr(&mn);
         q.b1 = to_fr(max_range);
         q.num_bits = (uint32_t)lay.num_bits;
         q.wvar = witness->var;
@@ -837,72 +867,41 @@ pg_status pg_range_check(pg_composer *c, const pg_scalar *min_range, const pg_sc
         blob_scalar(b, 0, &witness->scalar);
         b.w[4] = witness->var;
         PG_TRY(stage(c, b, 5));
-        pg::RangeCheckGD::Args A{};
-        A.min_range = to_fr(min_range);
-        A.max_range = to_fr(max_range);
-        A.n = (uint32_t)lay.num_bits;
-        A.witness = reinterpret_cast<const uint4 *>(c->stage_words());
-        A.witness_vars = c->stage_words() + 4;
-        A.pow2 = c->e->d_pow2.as<uint4>();
         const pg_columns at = cols_at(c, c->n, c->nvars);
-        PG_TRY(launch<pg::RangeCheckGD>(c->e, A, &at, 1, c->n, c->nvars, c->zero_var, nullptr, nullptr, c->stream, nullptr, sa.in_place));
+        const auto one_item = [&](auto gd, auto A) {  // what the two gadgets' Args share; the batch of one
+            A.max_range = to_fr(max_range);
+            A.n = (uint32_t)lay.num_bits;
+            A.witness = reinterpret_cast<const uint4 *>(c->stage_words());
+            A.witness_vars = c->stage_words() + 4;
+            A.pow2 = c->e->d_pow2.as<uint4>();
+            return launch<decltype(gd)>(c->e, A, &at, 1, c->n, c->nvars, c->zero_var, nullptr, nullptr, c->stream, nullptr, sa.in_place);
+        };
+        if (range_check) {
+            pg::RangeCheckGD::Args A{};
+            A.min_range = to_fr(&mn);
+            PG_TRY(one_item(pg::RangeCheckGD{}, A));
+        } else {
+            PG_TRY(one_item(pg::MaxBoundGD<false>{}, pg::MaxBoundGD<false>::Args{}));
+        }
     }
     sa.commit();
     c->n += rows;
     c->nvars += vars;
     *out = c->nvars - 1;  // composer.mul(1, y1, y2, 0) is the last variable, range.rs:42
+    if (num_bits) *num_bits = lay.num_bits;
     return PG_OK;
+}
+static_assert((uint32_t)SigKind::RANGE_CHECK == pg::WIRES_RANGE_CHECK && (uint32_t)SigKind::MAX_BOUND == pg::WIRES_MAX_BOUND,
+              "a single ladder call's SigKind is its Queued::kind, the wire kind of the fused call");
+
+pg_status pg_range_check(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
+                         const pg_allocated_scalar *witness, pg_variable *out) {
+    return single_ladder(c, SigKind::RANGE_CHECK, min_range, max_range, witness, out, nullptr);
 }
 
 pg_status pg_max_bound(pg_composer *c, const pg_scalar *max_range, const pg_allocated_scalar *witness, pg_variable *out,
                        uint64_t *num_bits) {
-    if (!c || !witness || !out) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!max_range) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
-    if (!(c->last_kind == 2 && std::memcmp(&c->last_max, max_range, 32) == 0)) {
-        c->last_kind = 0;
-        PG_TRY(pg_max_bound_layout(max_range, 1, &c->last_lay));
-        c->last_max = *max_range;
-        c->last_kind = 2;
-    }
-    const pg_layout lay = c->last_lay;
-    const uint64_t rows = lay.gates_per_item, vars = pg::kind_vars(pg::WIRES_MAX_BOUND_ALLOCATED, lay.num_bits);
-    PG_TRY(need(c, rows, vars));
-    PG_TRY(check_var(c, witness->var));
-    if (!is_reduced(to_fr(&witness->scalar))) return fail(PG_ERR_INVALID_ARGUMENT, "witness is not a reduced BlsScalar");
-    if (c->queueing && c->queue.size() >= PG_QUEUE_MAX) PG_TRY(flush(c));  // (before the decision: a flush can fail)
-    SignedAppend sa(c, gadget_sig(c, 2, pg::fr_zero(), to_fr(max_range), 1, witness->var), rows);
-    if (c->queueing) {
-        c->queue.emplace_back();
-        pg_composer::Queued &q = c->queue.back();
-        q.in_place = sa.in_place;
-        q.kind = 2;
-        q.b0 = pg::fr_zero();
-        q.b1 = to_fr(max_range);
-        q.num_bits = (uint32_t)lay.num_bits;
-        q.wvar = witness->var;
-        q.wval = to_fr(&witness->scalar);
-        q.gate = c->n;
-        q.var = c->nvars;
-    } else {
-        pg::StageBlob b{};
-        blob_scalar(b, 0, &witness->scalar);
-        b.w[4] = witness->var;
-        PG_TRY(stage(c, b, 5));
-        pg::MaxBoundGD<false>::Args A{};
-        A.max_range = to_fr(max_range);
-        A.n = (uint32_t)lay.num_bits;
-        A.witness = reinterpret_cast<const uint4 *>(c->stage_words());
-        A.witness_vars = c->stage_words() + 4;
-        A.pow2 = c->e->d_pow2.as<uint4>();
-        const pg_columns at = cols_at(c, c->n, c->nvars);
-        PG_TRY(launch<pg::MaxBoundGD<false>>(c->e, A, &at, 1, c->n, c->nvars, c->zero_var, nullptr, nullptr, c->stream, nullptr, sa.in_place));
-    }
-    sa.commit();
-    c->n += rows;
-    c->nvars += vars;
-    *out = c->nvars - 1;
-    if (num_bits) *num_bits = lay.num_bits;
-    return PG_OK;
+    return single_ladder(c, SigKind::MAX_BOUND, nullptr, max_range, witness, out, num_bits);
 }
 
 pg_status pg_scalar_decomposition_gadget(pg_composer *c, uint64_t num_bits, const pg_allocated_scalar *witness,
@@ -919,7 +918,7 @@ pg_status pg_scalar_decomposition_gadget(pg_composer *c, uint64_t num_bits, cons
     b.w[4] = witness->var;
     PG_TRY(stage(c, b, 5));
     const pg_columns at = cols_at(c, c->n, c->nvars);
-    SignedAppend sa(c, gadget_sig(c, 43, pg::fr_zero(), pg::fr_zero(), num_bits, witness->var), lay.n_gates);
+    SignedAppend sa(c, gadget_sig(c, SigKind::DECOMPOSITION, pg::fr_zero(), pg::fr_zero(), num_bits, witness->var), lay.n_gates);
     PG_TRY(decomposition_common(c->e, num_bits, c->stage_words() + 4, reinterpret_cast<const pg_scalar *>(c->stage_words()), 1, c->n, c->nvars, &at,
                                 nullptr, c->stream, sa.in_place));
     sa.commit();
@@ -1010,7 +1009,7 @@ namespace {
 // emit: its *_common call; sig_kind, b0, b1: what its signature hashes beside the batch and the place.  A kind whose witnesses are
 // Variables from elsewhere (the `_allocated` calls, decomposition) has their array checked and digested first.
 template <class Layout, class Emit>
-pg_status ladder_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg::Fr &b0, const pg::Fr &b1, const pg_variable *d_witness_var,
+pg_status ladder_batch(pg_composer *c, uint32_t wire_kind, SigKind sig_kind, const pg::Fr &b0, const pg::Fr &b1, const pg_variable *d_witness_var,
                        uint64_t batch, uint64_t *num_bits, Layout layout, Emit emit) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     PG_TRY(flush(c));
@@ -1034,7 +1033,7 @@ pg_status ladder_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, co
     if (num_bits) *num_bits = lay.num_bits;
     return PG_OK;
 }
-pg_status range_check_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg_scalar *min_range, const pg_scalar *max_range,
+pg_status range_check_batch(pg_composer *c, uint32_t wire_kind, SigKind sig_kind, const pg_scalar *min_range, const pg_scalar *max_range,
                             const pg_variable *d_witness_var, const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
     return ladder_batch(
         c, wire_kind, sig_kind, opt_fr(min_range), opt_fr(max_range), d_witness_var, batch, nullptr,
@@ -1043,7 +1042,7 @@ pg_status range_check_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kin
             return range_check_common(c->e, min_range, max_range, d_witness_var, d_witness, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
         });
 }
-pg_status max_bound_batch(pg_composer *c, uint32_t wire_kind, uint64_t sig_kind, const pg_scalar *max_range, const pg_variable *d_witness_var,
+pg_status max_bound_batch(pg_composer *c, uint32_t wire_kind, SigKind sig_kind, const pg_scalar *max_range, const pg_variable *d_witness_var,
                           const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars, uint64_t *num_bits) {
     return ladder_batch(
         c, wire_kind, sig_kind, pg::fr_zero(), opt_fr(max_range), d_witness_var, batch, num_bits,
@@ -1058,26 +1057,26 @@ extern "C" {
 
 pg_status pg_composer_range_check_batch(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
                                         const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
-    return range_check_batch(c, pg::WIRES_RANGE_CHECK, 11, min_range, max_range, nullptr, d_witness, batch, d_result_vars);
+    return range_check_batch(c, pg::WIRES_RANGE_CHECK, SigKind::RANGE_CHECK_BATCH, min_range, max_range, nullptr, d_witness, batch, d_result_vars);
 }
 pg_status pg_composer_range_check_allocated_batch(pg_composer *c, const pg_scalar *min_range, const pg_scalar *max_range,
                                                   const pg_variable *d_witness_var, const pg_scalar *d_witness,
                                                   uint64_t batch, pg_variable *d_result_vars) {
-    return range_check_batch(c, pg::WIRES_RANGE_CHECK_ALLOCATED, 21, min_range, max_range, d_witness_var, d_witness, batch, d_result_vars);
+    return range_check_batch(c, pg::WIRES_RANGE_CHECK_ALLOCATED, SigKind::RANGE_CHECK_ALLOCATED_BATCH, min_range, max_range, d_witness_var, d_witness, batch, d_result_vars);
 }
 pg_status pg_composer_max_bound_batch(pg_composer *c, const pg_scalar *max_range, const pg_scalar *d_witness, uint64_t batch,
                                       pg_variable *d_result_vars, uint64_t *num_bits) {
-    return max_bound_batch(c, pg::WIRES_MAX_BOUND, 12, max_range, nullptr, d_witness, batch, d_result_vars, num_bits);
+    return max_bound_batch(c, pg::WIRES_MAX_BOUND, SigKind::MAX_BOUND_BATCH, max_range, nullptr, d_witness, batch, d_result_vars, num_bits);
 }
 pg_status pg_composer_max_bound_allocated_batch(pg_composer *c, const pg_scalar *max_range, const pg_variable *d_witness_var,
                                                 const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars,
                                                 uint64_t *num_bits) {
-    return max_bound_batch(c, pg::WIRES_MAX_BOUND_ALLOCATED, 22, max_range, d_witness_var, d_witness, batch, d_result_vars, num_bits);
+    return max_bound_batch(c, pg::WIRES_MAX_BOUND_ALLOCATED, SigKind::MAX_BOUND_ALLOCATED_BATCH, max_range, d_witness_var, d_witness, batch, d_result_vars, num_bits);
 }
 pg_status pg_composer_scalar_decomposition_batch(pg_composer *c, uint64_t num_bits, const pg_variable *d_witness_var,
                                                  const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars) {
     return ladder_batch(
-        c, pg::WIRES_DECOMPOSITION, 23, pg::fr_from_u64(num_bits), pg::fr_zero(), d_witness_var, batch, nullptr,
+        c, pg::WIRES_DECOMPOSITION, SigKind::DECOMPOSITION_BATCH, pg::fr_from_u64(num_bits), pg::fr_zero(), d_witness_var, batch, nullptr,
         [&](pg_layout *lay) { return pg_scalar_decomposition_layout(num_bits, batch, lay); },
         [&](const pg_columns *at, bool in_place) {
             return decomposition_common(c->e, num_bits, d_witness_var, d_witness, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
@@ -1086,86 +1085,99 @@ pg_status pg_composer_scalar_decomposition_batch(pg_composer *c, uint64_t num_bi
 
 }  // extern "C"
 
-// the two-input scalar gadgets: assignments gathered from the composer's own table into its scratch, then the engine call
 namespace {
-template <class GD>
-pg_status two_input_batch(pg_composer *c, uint64_t kind, uint32_t wire_kind, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
-                          pg_variable *d_result_vars) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    const uint64_t rows = pg::kind_rows(wire_kind), vars = pg::kind_vars(wire_kind);
-    PG_TRY(flush(c));
-    if (batch == 0) return PG_OK;
-    PG_TRY(check_u64s(d_a_var, "first Variable array"));
-    PG_TRY(check_u64s(d_b_var, "second Variable array"));
-    pg_composer::Sig dg;
-    PG_TRY(check_var_arrays(c, {d_a_var, d_b_var}, batch, &dg));
-    PG_TRY(need(c, rows * batch, vars * batch));
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, c->val_ws, 2 * batch * 32));
-    uint4 *va = c->val_ws.as<uint4>(), *vb = va + 2 * batch;
-    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
-    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_a_var, c->cols.view().vars, batch, va);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_b_var, c->cols.view().vars, batch, vb);
+// dst[i] = the assignment of Variable d_var[i], from the composer's own table, on its stream (dst: in val_ws, sized by the caller)
+pg_status gather_values(pg_composer *c, const pg_variable *d_var, uint64_t batch, pg_scalar *dst) {
+    // (a lane moves 16 bytes, half an assignment: 2 * batch lanes' work)
+    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 32;
+    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, d_var,
+                       c->cols.view().vars, batch, reinterpret_cast<uint4 *>(dst));
     PG_HIP_TRY(hipGetLastError());
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    // (the rows: the two Variable arrays and where the call lands)
-    SignedAppend sa(c, gadget_sig(c, kind, pg::fr_zero(), pg::fr_zero(), batch, 0, dg), rows * batch);
-    PG_TRY(two_input_common<GD>(c->e, d_a_var, reinterpret_cast<const pg_scalar *>(va), d_b_var, reinterpret_cast<const pg_scalar *>(vb),
-                                batch, c->n, c->nvars, &at, d_result_vars, c->stream, sa.in_place));
-    sa.commit();
-    add_footprint(c, pg::footprint(c->n, c->nvars, batch, wire_kind));
-    c->n += rows * batch;
-    c->nvars += vars * batch;
     return PG_OK;
 }
-}  // namespace
 
-// the range widget on existing Variables (range_gate.hpp): assignments gathered from the composer's own table, then the emitter.  The
-// rows leave no footprint (sigma and the wire values take the generic routes); the composer remembers where q_range = 1.
-namespace {
-pg_status range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    if (num_bits < 2 || num_bits > 254 || (num_bits & 1))
-        return fail(PG_ERR_INVALID_ARGUMENT, "range_gate: num_bits must be even and in [2, 254], got " + std::to_string(num_bits));
-    const uint32_t k = (uint32_t)num_bits / 2, g = (k + 2) / 3;
-    const uint64_t rows = (uint64_t)(g + 1) * batch, vars = (uint64_t)(k - 1) * batch;
+// The appends on EXISTING Variables: `batch` items on the device arrays `arrays` (each with the name its errors give it), `rows` rows
+// and `vars` Variables at the composer's end.  Assignments are gathered from the composer's own table into its scratch, then the
+// engine call.
+//   check(&dg)                    every entry a Variable of this composer, and the digest of the arrays (check_var_arrays, or the call's
+//                                 own pass where other device arrays must be looked at in the same host synchronisation)
+//   sign(dg)                      the call's signature
+//   emit(&at, values, in_place)   its *_common call; values: the arrays' assignments, `batch` scalars per array in the list's order
+//   record()                      what the composer remembers of the rows (a footprint, range items); n and nvars are still the call's first
+template <class Check, class Sign, class Emit, class Record>
+pg_status var_batch(pg_composer *c, std::initializer_list<std::pair<const pg_variable *, const char *>> arrays, uint64_t batch, uint64_t rows,
+                    uint64_t vars, Check check, Sign sign, Emit emit, Record record) {
     PG_TRY(flush(c));
     if (batch == 0) return PG_OK;
-    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
+    for (const auto &a : arrays) PG_TRY(check_u64s(a.first, a.second));
     pg_composer::Sig dg;
-    PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
+    PG_TRY(check(&dg));
     PG_TRY(need(c, rows, vars));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
-    uint4 *val = c->val_ws.as<uint4>();
-    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
-    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_witness_var, c->cols.view().vars, batch, val);
-    PG_HIP_TRY(hipGetLastError());
+    PG_TRY(perm_reserve(c, c->val_ws, arrays.size() * batch * sizeof(pg_scalar)));
+    pg_scalar *const values = c->val_ws.as<pg_scalar>();
+    size_t i = 0;
+    for (const auto &a : arrays) PG_TRY(gather_values(c, a.first, batch, values + batch * i++));
     const pg_columns at = cols_at(c, c->n, c->nvars);
-    // (the rows: the Variable array, the bound and where the call lands)
-    SignedAppend sa(c, gadget_sig(c, 27, pg::fr_zero(), pg::fr_zero(), batch, num_bits, dg), rows);
-    PG_TRY(range_gate_common(c->e, d_witness_var, reinterpret_cast<const pg_scalar *>(val), (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var,
-                             &at, c->stream, sa.in_place));
+    SignedAppend sa(c, sign(dg), rows);
+    PG_TRY(emit(&at, values, sa.in_place));
     sa.commit();
-    pg::RangeSeg *last = c->range_segs.empty() ? nullptr : &c->range_segs.back();
-    if (last && last->g == g && last->first + last->items * (g + 1) == c->n) last->items += batch;
-    else c->range_segs.push_back(pg::RangeSeg{c->n, batch, g});
+    record();
     c->n += rows;
     c->nvars += vars;
     return PG_OK;
+}
+
+// the two-input scalar gadgets (the rows: the two Variable arrays and where the call lands)
+template <class GD>
+pg_status two_input_batch(pg_composer *c, SigKind kind, uint32_t wire_kind, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
+                          pg_variable *d_result_vars) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    return var_batch(
+        c, {{d_a_var, "first Variable array"}, {d_b_var, "second Variable array"}}, batch, pg::kind_rows(wire_kind) * batch,
+        pg::kind_vars(wire_kind) * batch, [&](pg_composer::Sig *dg) { return check_var_arrays(c, {d_a_var, d_b_var}, batch, dg); },
+        [&](const pg_composer::Sig &dg) { return gadget_sig(c, kind, pg::fr_zero(), pg::fr_zero(), batch, 0, dg); },
+        [&](const pg_columns *at, const pg_scalar *values, bool in_place) {
+            return two_input_common<GD>(c->e, d_a_var, values, d_b_var, values + batch, batch, c->n, c->nvars, at, d_result_vars, c->stream, in_place);
+        },
+        [&] { add_footprint(c, pg::footprint(c->n, c->nvars, batch, wire_kind)); });
+}
+
+// the widget rows [first_row, first_row + items * (g + 1)): continue the last range segment or begin one
+void note_range_items(pg_composer *c, uint64_t first_row, uint64_t items, uint32_t g) {
+    pg::RangeSeg *last = c->range_segs.empty() ? nullptr : &c->range_segs.back();
+    if (last && last->g == g && last->first + last->items * (g + 1) == first_row) last->items += items;
+    else c->range_segs.push_back(pg::RangeSeg{first_row, items, g});
+}
+
+pg_status widget_num_bits(const char *gate, uint64_t most, uint64_t num_bits) {
+    if (pg::widget_num_bits_ok(num_bits, most)) return PG_OK;
+    return fail(PG_ERR_INVALID_ARGUMENT, std::string(gate) + ": num_bits must be even and in [2, " + std::to_string(most) + "], got " +
+                                             std::to_string(num_bits));
+}
+pg_status range_num_bits(uint64_t num_bits) { return widget_num_bits("range_gate", pg::kRangeGateMaxBits, num_bits); }
+pg_status interval_num_bits(uint64_t num_bits) { return widget_num_bits("interval_gate", pg::kIntervalGateMaxBits, num_bits); }
+
+// the range widget on existing Variables (range_gate.hpp).  The rows leave no footprint (sigma and the wire values take the generic
+// routes); the composer remembers where q_range = 1.  The rows: the Variable array, num_bits and where the call lands.
+pg_status range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(range_num_bits(num_bits));
+    const pg::WidgetShape shape = pg::widget_shape(num_bits);
+    return var_batch(
+        c, {{d_witness_var, "d_witness_var"}}, batch, (uint64_t)shape.rows() * batch, (uint64_t)(shape.k - 1) * batch,
+        [&](pg_composer::Sig *dg) { return check_var_arrays(c, {d_witness_var}, batch, dg); },
+        [&](const pg_composer::Sig &dg) { return gadget_sig(c, SigKind::RANGE_GATE_BATCH, pg::fr_zero(), pg::fr_zero(), batch, num_bits, dg); },
+        [&](const pg_columns *at, const pg_scalar *values, bool in_place) {
+            return range_gate_common(c->e, d_witness_var, values, (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var, at, c->stream, in_place);
+        },
+        [&] { note_range_items(c, c->n, batch, shape.g); });
 }
 
 // the interval gadget on existing Variables (interval_gate.hpp): min <= witness <= max by two range widgets on the differences, whose
 // terminal rows carry the subtractions.  d_min / d_max: device arrays with a pair of bounds per item, or NULL: *min, *max for the call.
 // As range_gate_batch: assignments gathered from the composer's own table, no footprint, the widget rows remembered as 2 x batch
 // range items of g + 1 rows.
-pg_status interval_num_bits(uint64_t num_bits) {
-    if (num_bits < 2 || num_bits > 252 || (num_bits & 1))
-        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: num_bits must be even and in [2, 252], got " + std::to_string(num_bits));
-    return PG_OK;
-}
 // one public pair against the preconditions, as canonical integers
 pg_status interval_bounds(const pg_scalar *min, const pg_scalar *max, uint64_t num_bits) {
     PG_TRY(check_field(min, "min"));
@@ -1191,10 +1203,9 @@ pg_status check_interval_arrays(pg_composer *c, const pg_variable *d_witness_var
     unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 32);
     PG_HIP_TRY(hipMemsetAsync(d_out, 0, 64, c->stream));
     PG_HIP_TRY(hipMemsetAsync(d_out + 1, 0xff, 8, c->stream));
-    const uint64_t most = (uint64_t)c->e->num_cus * 8, want = (batch + pg::kThreads - 1) / pg::kThreads;
-    hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, d_witness_var,
-                       batch, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
-    const uint64_t few = (uint64_t)c->e->num_cus * 2;  // (its waves end in contended atomics: interval_gate.hpp)
+    digest_words(c, d_witness_var, batch, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
+    // (its waves end in contended atomics: interval_gate.hpp)
+    const uint64_t want = (batch + pg::kThreads - 1) / pg::kThreads, few = (uint64_t)c->e->num_cus * 2;
     hipLaunchKernelGGL(pg::interval_bounds_kernel, dim3((uint32_t)(want < few ? want : few)), dim3(pg::kThreads), 0, c->stream,
                        reinterpret_cast<const uint4 *>(d_min), reinterpret_cast<const uint4 *>(d_max), batch, (uint32_t)num_bits, d_out);
     PG_HIP_TRY(hipGetLastError());
@@ -1220,44 +1231,38 @@ pg_status interval_gate_batch(pg_composer *c, const pg_variable *d_witness_var, 
     const bool per_item = !min;
     if (!per_item) PG_TRY(interval_bounds(min, max, num_bits));
     if ((batch + 255) / 256 > 0xffffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "batch too large for one call");
-    const uint32_t k = (uint32_t)num_bits / 2, g = (k + 2) / 3;
-    const uint64_t rows = 2 * (uint64_t)(g + 1) * batch, vars = 2 * (uint64_t)k * batch;
+    const pg::WidgetShape shape = pg::widget_shape(num_bits);
+    // what the signature has for the bounds: the uniform call's two scalars, or (b0's first words) the digest of the two arrays
+    pg::Fr b0 = per_item ? pg::fr_zero() : to_fr(min), b1 = per_item ? pg::fr_zero() : to_fr(max);
+    return var_batch(
+        c, {{d_witness_var, "d_witness_var"}}, batch, 2 * (uint64_t)shape.rows() * batch, 2 * (uint64_t)shape.k * batch,
+        [&](pg_composer::Sig *dg) -> pg_status {
+            if (!per_item) return check_var_arrays(c, {d_witness_var}, batch, dg);
+            PG_TRY(check_scalars(d_min, "d_min"));
+            PG_TRY(check_scalars(d_max, "d_max"));
+            pg_composer::Sig bounds;
+            PG_TRY(check_interval_arrays(c, d_witness_var, d_min, d_max, num_bits, batch, dg, &bounds));
+            b0.l[0] = bounds.a;
+            b0.l[1] = bounds.b;
+            return PG_OK;
+        },
+        [&](const pg_composer::Sig &dg) {
+            return gadget_sig(c, per_item ? SigKind::INTERVAL_GATE_RAGGED_BATCH : SigKind::INTERVAL_GATE_BATCH, b0, b1, batch, num_bits, dg);
+        },
+        [&](const pg_columns *at, const pg_scalar *values, bool in_place) {
+            return interval_gate_common(c->e, d_witness_var, values, b0, b1, per_item ? d_min : nullptr, per_item ? d_max : nullptr,
+                                        (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var, at, c->stream, in_place);
+        },
+        [&] { note_range_items(c, c->n, 2 * batch, shape.g); });
+}
+// the single calls of the two widgets are batches of one: the Variable goes through the composer's staging words
+pg_status stage_variable(pg_composer *c, pg_variable witness) {
     PG_TRY(flush(c));
-    if (batch == 0) return PG_OK;
-    PG_TRY(check_u64s(d_witness_var, "d_witness_var"));
-    pg_composer::Sig dg, bounds{0, 0};
-    pg::Fr b0 = pg::fr_zero(), b1 = pg::fr_zero();
-    if (per_item) {
-        PG_TRY(check_scalars(d_min, "d_min"));
-        PG_TRY(check_scalars(d_max, "d_max"));
-        PG_TRY(check_interval_arrays(c, d_witness_var, d_min, d_max, num_bits, batch, &dg, &bounds));
-        b0.l[0] = bounds.a;  // (the arrays' digest where the uniform call signs its two scalars)
-        b0.l[1] = bounds.b;
-    } else {
-        PG_TRY(check_var_arrays(c, {d_witness_var}, batch, &dg));
-        b0 = to_fr(min);
-        b1 = to_fr(max);
-    }
-    PG_TRY(need(c, rows, vars));
+    PG_TRY(check_var(c, witness));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
-    uint4 *val = c->val_ws.as<uint4>();
-    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
-    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_witness_var, c->cols.view().vars, batch, val);
-    PG_HIP_TRY(hipGetLastError());
-    const pg_columns at = cols_at(c, c->n, c->nvars);
-    // (the rows: the Variable array, num_bits, the bounds and where the call lands)
-    SignedAppend sa(c, gadget_sig(c, per_item ? 62 : 61, b0, b1, batch, num_bits, dg), rows);
-    PG_TRY(interval_gate_common(c->e, d_witness_var, reinterpret_cast<const pg_scalar *>(val), b0, b1, per_item ? d_min : nullptr,
-                                per_item ? d_max : nullptr, (uint32_t)num_bits, batch, c->n, c->nvars, c->zero_var, &at, c->stream, sa.in_place));
-    sa.commit();
-    pg::RangeSeg *last = c->range_segs.empty() ? nullptr : &c->range_segs.back();
-    if (last && last->g == g && last->first + last->items * (g + 1) == c->n) last->items += 2 * batch;
-    else c->range_segs.push_back(pg::RangeSeg{c->n, 2 * batch, g});
-    c->n += rows;
-    c->nvars += vars;
-    return PG_OK;
+    pg::StageBlob b{};
+    b.w[0] = witness;
+    return stage(c, b, 1);
 }
 }  // namespace
 
@@ -1272,49 +1277,36 @@ pg_status pg_composer_interval_gate_ragged_batch(pg_composer *c, const pg_variab
                                                  const pg_scalar *d_max, uint64_t num_bits, uint64_t batch) {
     return interval_gate_batch(c, d_witness_var, nullptr, nullptr, d_min, d_max, num_bits, batch);
 }
-// a batch of one: the Variable goes through the composer's staging words
 pg_status pg_composer_interval_gate(pg_composer *c, pg_variable witness, const pg_scalar *min, const pg_scalar *max, uint64_t num_bits) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     if (!min || !max) return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: min or max is NULL");
     PG_TRY(interval_num_bits(num_bits));
     PG_TRY(interval_bounds(min, max, num_bits));
-    PG_TRY(flush(c));
-    PG_TRY(check_var(c, witness));
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    pg::StageBlob b{};
-    b.w[0] = witness;
-    PG_TRY(stage(c, b, 1));
+    PG_TRY(stage_variable(c, witness));
     return interval_gate_batch(c, c->stage_words(), min, max, nullptr, nullptr, num_bits, 1);
 }
 
 pg_status pg_composer_range_gate_batch(pg_composer *c, const pg_variable *d_witness_var, uint64_t num_bits, uint64_t batch) {
     return range_gate_batch(c, d_witness_var, num_bits, batch);
 }
-// a batch of one: the Variable goes through the composer's staging words
 pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t num_bits) {
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    if (num_bits < 2 || num_bits > 254 || (num_bits & 1))
-        return fail(PG_ERR_INVALID_ARGUMENT, "range_gate: num_bits must be even and in [2, 254], got " + std::to_string(num_bits));
-    PG_TRY(flush(c));
-    PG_TRY(check_var(c, witness));
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    pg::StageBlob b{};
-    b.w[0] = witness;
-    PG_TRY(stage(c, b, 1));
+    PG_TRY(range_num_bits(num_bits));
+    PG_TRY(stage_variable(c, witness));
     return range_gate_batch(c, c->stage_words(), num_bits, 1);
 }
 
 pg_status pg_composer_conditionally_select_zero_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_select_var,
                                                       uint64_t batch, pg_variable *d_result_vars) {
-    return two_input_batch<pg::SelectZeroGD>(c, 24, pg::WIRES_SELECT_ZERO, d_x_var, d_select_var, batch, d_result_vars);
+    return two_input_batch<pg::SelectZeroGD>(c, SigKind::SELECT_ZERO_BATCH, pg::WIRES_SELECT_ZERO, d_x_var, d_select_var, batch, d_result_vars);
 }
 pg_status pg_composer_conditionally_select_one_batch(pg_composer *c, const pg_variable *d_y_var, const pg_variable *d_selector_var,
                                                      uint64_t batch, pg_variable *d_result_vars) {
-    return two_input_batch<pg::SelectOneGD>(c, 25, pg::WIRES_SELECT_ONE, d_y_var, d_selector_var, batch, d_result_vars);
+    return two_input_batch<pg::SelectOneGD>(c, SigKind::SELECT_ONE_BATCH, pg::WIRES_SELECT_ONE, d_y_var, d_selector_var, batch, d_result_vars);
 }
 pg_status pg_composer_maybe_equal_batch(pg_composer *c, const pg_variable *d_a_var, const pg_variable *d_b_var, uint64_t batch,
                                         pg_variable *d_result_vars) {
-    return two_input_batch<pg::MaybeEqualGD>(c, 26, pg::WIRES_MAYBE_EQUAL, d_a_var, d_b_var, batch, d_result_vars);
+    return two_input_batch<pg::MaybeEqualGD>(c, SigKind::MAYBE_EQUAL_BATCH, pg::WIRES_MAYBE_EQUAL, d_a_var, d_b_var, batch, d_result_vars);
 }
 
 namespace {
@@ -1380,58 +1372,48 @@ uint64_t unmatched_if(pg_composer *c, uint64_t errs) { return errs ? 0x800000000
 
 extern "C" {
 
-pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_max_range, const pg_scalar *d_witness,
-                                             uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out) {
+// the two ladder batches with public bounds per item (WIRES_MAX_BOUND: d_min_range is not looked at).  The rows: the arrays of bounds
+// and where the call lands.
+static pg_status ragged_ladder_batch(pg_composer *c, uint32_t wire_kind, SigKind kind, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
+                                     const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out) {
+    const bool with_min = wire_kind == pg::WIRES_RANGE_CHECK;
     if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
     PG_TRY(flush(c));
     if (batch == 0) return PG_OK;
+    if (with_min) PG_TRY(check_scalars(d_min_range, "d_min_range"));  // (digested before the engine call that checks the others)
     PG_HIP_TRY(hipSetDevice(c->e->device));
     return ragged_batch(
-        c, pg::WIRES_MAX_BOUND, batch, nullptr,
+        c, wire_kind, batch, nullptr,
         [&](RaggedBuffers &b, pg_layout *lay, uint64_t *) {
-            return pg_max_bound_ragged_plan(c->e, d_max_range, batch, b.bits(), b.rows(), b.vars(), lay, c->stream);
+            return (with_min ? pg_range_check_ragged_plan : pg_max_bound_ragged_plan)(c->e, d_max_range, batch, b.bits(), b.rows(), b.vars(), lay,
+                                                                                       c->stream);
         },
-        [&](uint64_t, pg_composer::Sig *sig) {  // the rows: the per-item public bounds and where the call lands
+        [&](uint64_t, pg_composer::Sig *sig) {
             pg_composer::Sig dg;
-            PG_TRY(digest_scalars(c, d_max_range, batch, &dg));
-            *sig = gadget_sig(c, 27, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
+            PG_TRY(digest_scalars(c, d_max_range, batch, &dg, with_min ? d_min_range : nullptr));
+            *sig = gadget_sig(c, kind, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
-            PG_TRY(max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at, d_result_vars,
-                                           c->stream, in_place));
+            PG_TRY(with_min ? range_check_ragged_common(c->e, d_min_range, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars,
+                                                        at, d_result_vars, c->stream, in_place)
+                            : max_bound_ragged_common(c->e, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at,
+                                                      d_result_vars, c->stream, in_place));
             if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits.get(), batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
                 return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
             return PG_OK;
         });
 }
-
+pg_status pg_composer_max_bound_ragged_batch(pg_composer *c, const pg_scalar *d_max_range, const pg_scalar *d_witness,
+                                             uint64_t batch, pg_variable *d_result_vars, uint32_t *d_num_bits_out) {
+    return ragged_ladder_batch(c, pg::WIRES_MAX_BOUND, SigKind::MAX_BOUND_RAGGED_BATCH, nullptr, d_max_range, d_witness, batch, d_result_vars,
+                               d_num_bits_out);
+}
 pg_status pg_composer_range_check_ragged_batch(pg_composer *c, const pg_scalar *d_min_range, const pg_scalar *d_max_range,
                                                const pg_scalar *d_witness, uint64_t batch, pg_variable *d_result_vars,
                                                uint32_t *d_num_bits_out) {
-    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
-    PG_TRY(flush(c));
-    if (batch == 0) return PG_OK;
-    PG_TRY(check_scalars(d_min_range, "d_min_range"));  // (digested before the engine call that checks the others)
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    return ragged_batch(
-        c, pg::WIRES_RANGE_CHECK, batch, nullptr,
-        [&](RaggedBuffers &b, pg_layout *lay, uint64_t *) {
-            return pg_range_check_ragged_plan(c->e, d_max_range, batch, b.bits(), b.rows(), b.vars(), lay, c->stream);
-        },
-        [&](uint64_t, pg_composer::Sig *sig) {  // the rows: both arrays of per-item public bounds and where the call lands
-            pg_composer::Sig dg;
-            PG_TRY(digest_scalars(c, d_max_range, batch, &dg, d_min_range));
-            *sig = gadget_sig(c, 30, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
-            return PG_OK;
-        },
-        [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
-            PG_TRY(range_check_ragged_common(c->e, d_min_range, d_max_range, d_witness, batch, b.bits(), b.rows(), b.vars(), c->n, c->nvars, at,
-                                             d_result_vars, c->stream, in_place));
-            if (d_num_bits_out && hipMemcpyAsync(d_num_bits_out, b.num_bits.get(), batch * 4, hipMemcpyDeviceToDevice, c->stream) != hipSuccess)
-                return fail(PG_ERR_HIP, "copy of the ladder lengths failed");
-            return PG_OK;
-        });
+    return ragged_ladder_batch(c, pg::WIRES_RANGE_CHECK, SigKind::RANGE_CHECK_RAGGED_BATCH, d_min_range, d_max_range, d_witness, batch,
+                               d_result_vars, d_num_bits_out);
 }
 
 pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask,
@@ -1444,20 +1426,16 @@ pg_status pg_composer_is_non_zero_batch(pg_composer *c, const pg_variable *d_var
     pg_composer::Sig dg;
     PG_TRY(check_var_arrays(c, {d_var}, batch, &dg));
     PG_HIP_TRY(hipSetDevice(c->e->device));
-    PG_TRY(perm_reserve(c, c->val_ws, batch * 32));
-    uint4 *vals = c->val_ws.as<uint4>();
-    const uint64_t want = (2 * batch + pg::kThreads - 1) / pg::kThreads;
-    const uint32_t grid = (uint32_t)(want < (uint64_t)c->e->num_cus * 32 ? want : (uint64_t)c->e->num_cus * 32);
-    hipLaunchKernelGGL(pg::gather_wire_values_kernel, dim3(grid), dim3(pg::kThreads), 0, c->stream, d_var, c->cols.view().vars, batch, vals);
-    PG_HIP_TRY(hipGetLastError());
-    const pg_scalar *d_vals = reinterpret_cast<const pg_scalar *>(vals);
+    PG_TRY(perm_reserve(c, c->val_ws, batch * sizeof(pg_scalar)));
+    pg_scalar *const d_vals = c->val_ws.as<pg_scalar>();
+    PG_TRY(gather_values(c, d_var, batch, d_vals));
     return ragged_batch(
         c, pg::WIRES_IS_NON_ZERO, batch, err_count,
         [&](RaggedBuffers &b, pg_layout *lay, uint64_t *errs) {
             return pg_is_non_zero_plan(c->e, d_vals, batch, b.rows(), b.vars(), d_err_mask, lay, errs, c->stream);
         },
         [&](uint64_t errs, pg_composer::Sig *sig) {
-            *sig = gadget_sig(c, 28, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs), dg);
+            *sig = gadget_sig(c, SigKind::IS_NON_ZERO_BATCH, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs), dg);
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
@@ -1479,7 +1457,7 @@ pg_status pg_composer_scalar_mix_batch(pg_composer *c, const pg_scalar *d_v, con
             return pg_scalar_mix_plan(c->e, d_v, batch, b.rows(), b.vars(), d_err_mask, lay, errs, c->stream);
         },
         [&](uint64_t errs, pg_composer::Sig *sig) {
-            *sig = gadget_sig(c, 13, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs));
+            *sig = gadget_sig(c, SigKind::SCALAR_MIX_BATCH, pg::fr_zero(), pg::fr_zero(), batch, unmatched_if(c, errs));
             return PG_OK;
         },
         [&](RaggedBuffers &b, const pg_columns *at, bool in_place) {
@@ -1508,7 +1486,7 @@ pg_status gate_batch(pg_composer *c, uint32_t op, const pg_variable *d_a, const 
     PG_HIP_TRY(hipSetDevice(c->e->device));
     // the rows: the selectors, the Variable arrays (and which of them are one and the same), where the call lands
     SigHasher h;
-    h.u64(29); h.u64(op); h.u64(batch); h.u64((d_b == d_a ? 1 : 0) | (!creates && d_c == d_a ? 2 : 0) | (!creates && d_c == d_b ? 4 : 0));
+    h.u64((uint64_t)SigKind::GATE_BATCH); h.u64(op); h.u64(batch); h.u64((d_b == d_a ? 1 : 0) | (!creates && d_c == d_a ? 2 : 0) | (!creates && d_c == d_b ? 4 : 0));
     h.fr(q_m); h.fr(q_l); h.fr(q_r); h.fr(q_o); h.fr(q_c); h.u64(dg.a); h.u64(dg.b);
     h.u64(c->n); h.u64(c->nvars); h.u64(c->zero_var);
     SignedAppend sa(c, h.done(), batch);

@@ -36,6 +36,27 @@ PG_HD Fr raw_shr(const Fr &c, uint32_t s) {
     return Fr{{l0, l1, l2, l3}};
 }
 
+// the widget's shape for num_bits (the comment above): what the host sizes a call by and the Args below are filled from
+struct WidgetShape {
+    uint32_t k, g, pad;  // quads, widget rows, leading positions that are zero_var beside P(0)
+    constexpr uint32_t rows() const { return g + 1; }  // of one widget: its g rows and the terminal row
+};
+constexpr WidgetShape widget_shape(uint64_t num_bits) {
+    const uint32_t k = (uint32_t)(num_bits / 2), g = (k + 2) / 3;
+    return WidgetShape{k, g, 3 * g - k};
+}
+// num_bits a widget can take: even, 2 .. most -- range_gate's own bound, and interval_gate's (interval_gate.hpp: 2^(num_bits + 1) < r)
+constexpr uint64_t kRangeGateMaxBits = 254, kIntervalGateMaxBits = 252;
+constexpr bool widget_num_bits_ok(uint64_t num_bits, uint64_t most) { return num_bits >= 2 && num_bits <= most && !(num_bits & 1); }
+constexpr bool widget_shape_is(uint64_t num_bits, uint32_t k, uint32_t g, uint32_t pad) {
+    return widget_shape(num_bits).k == k && widget_shape(num_bits).g == g && widget_shape(num_bits).pad == pad;
+}
+static_assert(widget_shape_is(2, 1, 1, 2), "one quad: no new Variable, P(0) .. P(2) are zero_var");
+static_assert(widget_shape_is(6, 3, 1, 0), "a full row: no padding");
+static_assert(widget_shape_is(8, 4, 2, 2), "the fourth quad opens a second row");
+static_assert(widget_shape_is(254, 127, 43, 2) && widget_shape(254).rows() == 44, "the longest chain that cannot wrap");
+static_assert(widget_num_bits_ok(2, 254) && widget_num_bits_ok(254, 254) && !widget_num_bits_ok(254, 252) && !widget_num_bits_ok(7, 254), "");
+
 struct RangeGateArgs {
     const uint64_t *witness_vars;  // existing Variables
     const uint4 *witness;          // their assignments (gathered from the composer's table)

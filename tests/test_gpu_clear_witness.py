@@ -452,3 +452,274 @@ def test_a_failed_append_leaves_no_signature(engine):
         for w in wits_a:
             ora.L.max_bound(ora.c, F(bound), ora.allocate(w), None)
     same(dev, ora)
+
+
+# ---- every batched append of StandardComposer, three items each, on a composer that holds nothing but eight allocated inputs ------------
+# An entry is (name, call): call(dev, ora, first, seed) makes the append on the device composer and, where the oracle has the gadget and
+# `ora` is given, on the oracle's.  Everything PUBLIC is the same in every build (which Variables, bounds, selectors, num_bits);
+# witness scalars come from `seed`, the inputs' (Variables first .. first + 7) and the call's own.  The inputs are 1 .. 60000: non-zero
+# (is_non_zero), below 2^16 (range_gate) and inside the intervals.  add_input_batch is not in the table: it appends no row and leaves
+# no signature.
+N_INPUTS, BATCH = 8, 3
+tv = lambda xs: torch.tensor(xs, dtype=torch.int64, device="cuda:0")
+ints = lambda n, seed, below: [int(v) % below for v in synth.splitmix64(n, seed)]
+RAGGED_MAX = [200, 2**40 + 1, 77]
+RAGGED_MIN = [3, 2**20, 0]
+IV_MIN, IV_MAX = [0, 1, 1], [2**16 - 1, 2**16, 60_001]
+
+
+def input_ints(seed):
+    return [1 + v for v in ints(N_INPUTS, seed + 5000, 60_000)]
+
+
+def build(dev, ora, call, seed, **kw):
+    """the eight inputs, then the append; what the append returns"""
+    w = synth.scalars_from_ints(input_ints(seed))
+    first = dev.add_input_batch(t(w))
+    if ora is not None:
+        assert [int(ora.allocate(x).var) for x in w][0] == first
+    return call(dev, ora, first, seed, **kw)
+
+
+def own(first, vs, seed):
+    """the assignments of some of the inputs: as the oracle's Fr, and as the device array a call on allocated witnesses wants"""
+    vals = [input_ints(seed)[v - first] for v in vs]
+    return [F(x) for x in vals], synth.scalars_from_ints(vals)
+
+
+def same_vars(r, o):
+    assert r.cpu().numpy().view(np.uint64).tolist() == [int(x) for x in o]
+
+
+def a_rc(dev, ora, first, seed):
+    w = synth.scalars_from_ints(ints(BATCH, seed, 300_000))
+    r = dev.range_check_batch(S(50_000), S(250_000), t(w))
+    if ora is not None:
+        same_vars(r, [ora.L.range_check(ora.c, F(50_000), F(250_000), ora.allocate(x)) for x in w])
+
+
+def a_rc_alloc(dev, ora, first, seed):
+    from oracle import pyoracle as po
+    vs = [first + 1, first + 4, first + 6]
+    vals, wv = own(first, vs, seed)
+    r = dev.range_check_allocated_batch(S(5), S(2**30), tv(vs), t(wv))
+    if ora is not None:
+        same_vars(r, [ora.L.range_check(ora.c, F(5), F(2**30), po.AllocatedScalar(v, x)) for v, x in zip(vs, vals)])
+
+
+def a_mb(dev, ora, first, seed):
+    w = synth.scalars_from_ints(ints(BATCH, seed, 2 * 10**9))
+    r, _ = dev.max_bound_batch(S(10**9), t(w))
+    if ora is not None:
+        same_vars(r, [ora.L.max_bound(ora.c, F(10**9), ora.allocate(x), None) for x in w])
+
+
+def a_mb_alloc(dev, ora, first, seed):
+    from oracle import pyoracle as po
+    vs = [first + 2, first, first + 7]
+    vals, wv = own(first, vs, seed)
+    r, _ = dev.max_bound_allocated_batch(S(40_000), tv(vs), t(wv))
+    if ora is not None:
+        same_vars(r, [ora.L.max_bound(ora.c, F(40_000), po.AllocatedScalar(v, x), None) for v, x in zip(vs, vals)])
+
+
+def a_mb_ragged(dev, ora, first, seed):
+    w = synth.scalars_from_ints(ints(BATCH, seed, 2**41))
+    r, _ = dev.max_bound_ragged_batch(t(synth.scalars_from_ints(RAGGED_MAX)), t(w))
+    if ora is not None:
+        same_vars(r, [ora.L.max_bound(ora.c, F(b), ora.allocate(x), None) for b, x in zip(RAGGED_MAX, w)])
+
+
+def a_rc_ragged(dev, ora, first, seed):
+    w = synth.scalars_from_ints(ints(BATCH, seed, 2**41))
+    r, _ = dev.range_check_ragged_batch(t(synth.scalars_from_ints(RAGGED_MIN)), t(synth.scalars_from_ints(RAGGED_MAX)), t(w))
+    if ora is not None:
+        same_vars(r, [ora.L.range_check(ora.c, F(lo), F(hi), ora.allocate(x)) for lo, hi, x in zip(RAGGED_MIN, RAGGED_MAX, w)])
+
+
+def a_dec(dev, ora, first, seed):
+    from oracle import pyoracle as po
+    vs = [first + 3, first + 5, first + 1]
+    vals, wv = own(first, vs, seed)
+    r = dev.scalar_decomposition_batch(16, tv(vs), t(wv))
+    if ora is not None:
+        same_vars(r, [ora.L.scalar_decomposition_gadget(ora.c, 16, po.AllocatedScalar(v, x), None) for v, x in zip(vs, vals)])
+
+
+def two_input(name):
+    def call(dev, ora, first, seed):
+        from oracle import pyoracle as po
+        a, b = [first, first + 1, first + 2], [first + 3, first + 4, first]
+        r = getattr(dev, name + "_batch")(tv(a), tv(b))
+        if ora is not None and name == "maybe_equal":
+            same_vars(r, [ora.L.maybe_equal(ora.c, po.AllocatedScalar(x, ora.L.composer_value(ora.c, x)),
+                                            po.AllocatedScalar(y, ora.L.composer_value(ora.c, y))) for x, y in zip(a, b)])
+        elif ora is not None:
+            same_vars(r, [getattr(ora.L, name)(ora.c, x, y) for x, y in zip(a, b)])
+    return call
+
+
+def a_inz(dev, ora, first, seed, with_zero_var=False):
+    vs = [first + 5, dev.zero_var if with_zero_var else first + 6, first + 7]
+    err, nerr = dev.is_non_zero_batch(tv(vs))
+    if ora is not None:
+        o = [int(ora.L.is_non_zero(ora.c, v, ora.L.composer_value(ora.c, v))) for v in vs]
+        assert err.cpu().numpy().tolist() == o and nerr == sum(o)
+    return nerr
+
+
+def a_mix(dev, ora, first, seed, zeros=()):
+    from oracle import pyoracle as po
+    import test_gpu_gadgets as tg
+    v, y, s, a, b = tg.mix_inputs(BATCH, seed, zeros)
+    _, _, nerr = dev.scalar_mix_batch(t(v), t(y), t(s), t(a), t(b))
+    for i in range(BATCH if ora is not None else 0):
+        vv, yy, ss = ora.add_input(v[i]), ora.add_input(y[i]), ora.add_input(s[i])
+        aa, bb = ora.allocate(a[i]), ora.allocate(b[i])
+        ora.L.is_non_zero(ora.c, vv, po.fr(v[i]))
+        ora.L.conditionally_select_one(ora.c, yy, ss)
+        ora.L.maybe_equal(ora.c, aa, bb)
+    return nerr
+
+
+def a_poly_b(dev, ora, first, seed):
+    a, b, c3 = [first, first + 1, first + 2], [first + 1, first + 1, first + 3], [first + 7, first + 6, first + 5]
+    q = [3, Q - 1, 0, 1, 77]
+    dev.poly_gate_batch(tv(a), tv(b), tv(c3), *[S(x) for x in q])
+    for x, y, z in zip(a, b, c3) if ora is not None else ():
+        ora.L.composer_poly_gate(ora.c, x, y, z, *[F(sel) for sel in q], None)
+
+
+def a_add_b(dev, ora, first, seed):
+    a, b = [first, first + 1, first + 2], [first + 3, first + 4, first]
+    r = dev.add_batch(S(3), tv(a), S(Q - 1), tv(b), S(9))
+    if ora is not None:
+        same_vars(r, [ora.L.composer_add(ora.c, F(3), x, F(Q - 1), y, F(9), None) for x, y in zip(a, b)])
+
+
+def a_mul_b(dev, ora, first, seed):
+    a, b = [first, first + 1, first + 2], [first + 3, first + 4, first]
+    r = dev.mul_batch(S(3), tv(a), tv(b), S(9))
+    if ora is not None:
+        same_vars(r, [ora.L.composer_mul(ora.c, F(3), x, y, F(9), None) for x, y in zip(a, b)])
+
+
+def a_ctc_b(dev, ora, first, seed):
+    a = [first, first + 1, first + 2]
+    dev.constrain_to_constant_batch(tv(a), S(12345))
+    for x in a if ora is not None else ():
+        ora.L.composer_constrain_to_constant(ora.c, x, F(12345), None)
+
+
+def a_bool_b(dev, ora, first, seed):
+    a = [first, first + 1, first + 2]
+    dev.boolean_gate_batch(tv(a))
+    for x in a if ora is not None else ():
+        ora.L.composer_boolean_gate(ora.c, x)
+
+
+# the widgets (the oracle has neither): the statement must hold on every row and the rows are counted.  num_bits = 16: k = 8 quads,
+# g = 3 widget rows and the terminal row -- 4 rows an item, twice that for the two halves of an interval
+def a_range_gate_b(dev, ora, first, seed):
+    dev.range_gate_batch(tv([first + 2, first + 3, first + 4]), 16)
+
+
+def a_range_gate(dev, ora, first, seed):
+    for v in (first + 2, first + 3, first + 4):
+        dev.range_gate(v, 16)
+
+
+def a_interval_b(dev, ora, first, seed):
+    dev.interval_gate_batch(tv([first + 2, first + 3, first + 4]), S(1), S(2**16), 16)
+
+
+def a_interval_ragged(dev, ora, first, seed):
+    dev.interval_gate_ragged_batch(tv([first + 2, first + 3, first + 4]), t(synth.scalars_from_ints(IV_MIN)), t(synth.scalars_from_ints(IV_MAX)), 16)
+
+
+def a_interval(dev, ora, first, seed):
+    for v in (first + 2, first + 3, first + 4):
+        dev.interval_gate(v, S(1), S(2**16), 16)
+
+
+WIDGET_ROWS = {"range_gate_batch": 4 * BATCH, "range_gate": 4 * BATCH, "interval_gate_batch": 8 * BATCH,
+               "interval_gate_ragged_batch": 8 * BATCH, "interval_gate": 8 * BATCH}
+# neighbours in the table are the calls most alike: the next entry is the "different call at the same place"
+SIGNED_APPENDS = [
+    ("range_check_batch", a_rc), ("range_check_ragged_batch", a_rc_ragged), ("range_check_allocated_batch", a_rc_alloc),
+    ("max_bound_allocated_batch", a_mb_alloc), ("max_bound_batch", a_mb), ("max_bound_ragged_batch", a_mb_ragged),
+    ("range_gate_batch", a_range_gate_b), ("range_gate", a_range_gate), ("interval_gate", a_interval),
+    ("interval_gate_batch", a_interval_b), ("interval_gate_ragged_batch", a_interval_ragged),
+    ("scalar_decomposition_batch", a_dec), ("is_non_zero_batch", a_inz), ("scalar_mix_batch", a_mix),
+    ("conditionally_select_zero_batch", two_input("conditionally_select_zero")),
+    ("conditionally_select_one_batch", two_input("conditionally_select_one")), ("maybe_equal_batch", two_input("maybe_equal")),
+    ("add_batch", a_add_b), ("mul_batch", a_mul_b), ("poly_gate_batch", a_poly_b),
+    ("constrain_to_constant_batch", a_ctc_b), ("boolean_gate_batch", a_bool_b),
+]
+
+
+def test_the_table_holds_every_batched_append():
+    """a batched append added to StandardComposer must be added to SIGNED_APPENDS"""
+    names = {n for n in vars(pg.StandardComposer) if n.endswith("_batch") and not n.startswith("_")} - {"add_input_batch"}
+    assert names | {"range_gate", "interval_gate"} == {n for n, _ in SIGNED_APPENDS}
+
+
+def test_signatures_tell_every_batched_append_apart(engine):
+    """What the signatures of the witness refresh protect, for every batched append (and the single range_gate / interval_gate), three
+    items each behind eight allocated inputs.  The SAME call on other witnesses finds all its rows in place, writes none again, and
+    leaves the composer the oracle's would be (the widgets, which the oracle lacks: every row's statement holds, and the rows are
+    counted).  A DIFFERENT call at the same place with the same batch -- the next of the table -- finds nothing in place and ends
+    the refresh: rows of another append must never be taken for one's own."""
+    from oracle import pyoracle as po
+    for i, (name, call) in enumerate(SIGNED_APPENDS):
+        dev = pg.StandardComposer(engine, 1 << 11, 1 << 12)
+        build(dev, None, call, 100 + i)
+        rows = dev.circuit_size() - 3
+        assert rows > 0 and rows == WIDGET_ROWS.get(name, rows), (name, rows)
+        dev.clear_witness()
+        ora = po.Composer() if name not in WIDGET_ROWS else None
+        build(dev, ora, call, 200 + i)
+        assert dev.refresh_stats() == (rows, 0, True), (name, dev.refresh_stats())
+        if ora is not None:
+            same(dev, ora)
+            assert dev.check() == ora.check(), name
+        else:
+            assert dev.check() == -1 and dev.circuit_size() == 3 + rows, name
+        dev.clear_witness()
+        other, other_call = SIGNED_APPENDS[(i + 1) % len(SIGNED_APPENDS)]
+        build(dev, None, other_call, 300 + i)
+        kept, rewritten, refreshing = dev.refresh_stats()
+        assert kept == 0 and rewritten == dev.circuit_size() - 3 and not refreshing, (name, other, kept, rewritten, refreshing)
+        dev.close()
+
+
+@pytest.mark.parametrize("order", [(a_range_gate_b, a_mb_ragged), (a_mb_ragged, a_range_gate_b)], ids=["widget_first", "ladder_first"])
+def test_range_gate_and_ragged_max_bound_are_told_apart(engine, order):
+    """the two appends that once signed with the same kind, one after the other at the same place with the same batch"""
+    first_call, second_call = order
+    dev = pg.StandardComposer(engine, 1 << 11, 1 << 12)
+    build(dev, None, first_call, 1)
+    dev.clear_witness()
+    build(dev, None, second_call, 2)
+    kept, rewritten, refreshing = dev.refresh_stats()
+    assert kept == 0 and rewritten == dev.circuit_size() - 3 and not refreshing
+    assert dev.check() == -1
+    dev.clear_witness()  # ... and what the second left is its own: the same call again is a refresh
+    build(dev, None, second_call, 3)
+    assert dev.refresh_stats() == (dev.circuit_size() - 3, 0, True)
+
+
+def test_a_batch_with_a_failing_item_is_never_matched(engine):
+    """scalar_mix_batch and is_non_zero_batch with an item that stops at its error (a shape that depends on a witness): the same
+    call again, failing at the same item, is not found in place, nor is the call without a failing item afterwards"""
+    from oracle import pyoracle as po
+    for call, bad in ((a_mix, {"zeros": (1,)}), (a_inz, {"with_zero_var": True})):
+        dev = pg.StandardComposer(engine, 1 << 11, 1 << 12)
+        for nth in range(3):
+            if nth:
+                dev.clear_witness()
+            ora = po.Composer()
+            assert build(dev, ora, call, 50 + nth, **({} if nth == 2 else bad)) == (0 if nth == 2 else 1)
+            kept, rewritten, refreshing = dev.refresh_stats()
+            assert kept == 0 and rewritten == dev.circuit_size() - 3 and not refreshing, (call.__name__, nth)
+            same(dev, ora)
