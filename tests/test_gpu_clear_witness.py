@@ -306,6 +306,26 @@ def test_fuzz_programs_rebuilt_on_other_witnesses(engine, seed):
         assert kept_total > 0, f"seed {seed}: appends {ops[:cut]} before the first witness-dependent shape, yet no row was found in place"
 
 
+@pytest.mark.parametrize("seed", [1, 19, 24, 103])
+def test_fuzz_widget_programs_rebuilt_on_other_witnesses(engine, seed):
+    """tests/widget_programs.py's random programs with range_gate / interval_gate calls in them (no item of theirs has a shape that
+    depends on a witness): built, then clear_witness and the SAME program on other witnesses, twice -- every row is found in place
+    and none is written again, and the composer == a fresh oracle replay of that build: columns, first failing row, q_range, sigma"""
+    from tests import widget_programs as wp
+    dev = pg.StandardComposer(engine, 1 << 14, 1 << 14)
+    dev.auto_grow()
+    for build, wit_seed in enumerate((1000 + seed, 2000 + seed, 3000 + seed)):
+        if build:
+            dev.clear_witness()
+        both = wp.run_widget_program(dev, None, seed, wit_seed)
+        stats = dev.refresh_stats()
+        try:
+            assert stats == (dev.circuit_size() - 3, 0, True) if build else stats[0] == 0
+            wp.assert_device_equals_oracle(both)
+        except AssertionError as e:
+            raise AssertionError(f"seed {seed}, build {build} (kept, rewritten, refreshing = {stats}), program {[c[:3] for c in both.log]}: {e}")
+
+
 def test_appends_on_device_arrays_are_signed_by_their_contents(engine):
     """batched appends whose rows depend on device arrays -- Variables (maybe_equal, select, gate batches, gadgets on allocated
     witnesses) and per-item bounds (ragged max_bound): rebuilt with the SAME arrays they are found in place (a bent limb in
@@ -618,28 +638,46 @@ def a_bool_b(dev, ora, first, seed):
         ora.L.composer_boolean_gate(ora.c, x)
 
 
-# the widgets (the oracle has neither): the statement must hold on every row and the rows are counted.  num_bits = 16: k = 8 quads,
-# g = 3 widget rows and the terminal row -- 4 rows an item, twice that for the two halves of an interval
+# the widgets, replayed on the oracle row for row (tests/widget_oracle.py; the Widgets object, which knows the q_range rows, rides on the
+# oracle composer).  num_bits = 16: k = 8 quads, g = 3 widget rows and the terminal row -- 4 rows an item, twice that for the two halves
+# of an interval
+def widgets_of(ora):
+    from tests import widget_oracle as wo
+    if not hasattr(ora, "widgets"):
+        ora.widgets = wo.Widgets()
+    return ora.widgets
+
+
 def a_range_gate_b(dev, ora, first, seed):
     dev.range_gate_batch(tv([first + 2, first + 3, first + 4]), 16)
+    if ora is not None:
+        widgets_of(ora).range_gate_batch(ora, [first + 2, first + 3, first + 4], 16)
 
 
 def a_range_gate(dev, ora, first, seed):
     for v in (first + 2, first + 3, first + 4):
         dev.range_gate(v, 16)
+        if ora is not None:
+            widgets_of(ora).range_gate(ora, v, 16)
 
 
 def a_interval_b(dev, ora, first, seed):
     dev.interval_gate_batch(tv([first + 2, first + 3, first + 4]), S(1), S(2**16), 16)
+    if ora is not None:
+        widgets_of(ora).interval_gate_batch(ora, [first + 2, first + 3, first + 4], 1, 2**16, 16)
 
 
 def a_interval_ragged(dev, ora, first, seed):
     dev.interval_gate_ragged_batch(tv([first + 2, first + 3, first + 4]), t(synth.scalars_from_ints(IV_MIN)), t(synth.scalars_from_ints(IV_MAX)), 16)
+    if ora is not None:
+        widgets_of(ora).interval_gate_ragged_batch(ora, [first + 2, first + 3, first + 4], IV_MIN, IV_MAX, 16)
 
 
 def a_interval(dev, ora, first, seed):
     for v in (first + 2, first + 3, first + 4):
         dev.interval_gate(v, S(1), S(2**16), 16)
+        if ora is not None:
+            widgets_of(ora).interval_gate(ora, v, 1, 2**16, 16)
 
 
 WIDGET_ROWS = {"range_gate_batch": 4 * BATCH, "range_gate": 4 * BATCH, "interval_gate_batch": 8 * BATCH,
@@ -667,9 +705,9 @@ def test_the_table_holds_every_batched_append():
 def test_signatures_tell_every_batched_append_apart(engine):
     """What the signatures of the witness refresh protect, for every batched append (and the single range_gate / interval_gate), three
     items each behind eight allocated inputs.  The SAME call on other witnesses finds all its rows in place, writes none again, and
-    leaves the composer the oracle's would be (the widgets, which the oracle lacks: every row's statement holds, and the rows are
-    counted).  A DIFFERENT call at the same place with the same batch -- the next of the table -- finds nothing in place and ends
-    the refresh: rows of another append must never be taken for one's own."""
+    leaves the composer the oracle's would be, its first failing row too (the widgets replayed on the oracle by tests/widget_oracle.py,
+    their rows counted besides).  A DIFFERENT call at the same place with the same batch -- the next of the table -- finds nothing in
+    place and ends the refresh: rows of another append must never be taken for one's own."""
     from oracle import pyoracle as po
     for i, (name, call) in enumerate(SIGNED_APPENDS):
         dev = pg.StandardComposer(engine, 1 << 11, 1 << 12)
@@ -677,14 +715,15 @@ def test_signatures_tell_every_batched_append_apart(engine):
         rows = dev.circuit_size() - 3
         assert rows > 0 and rows == WIDGET_ROWS.get(name, rows), (name, rows)
         dev.clear_witness()
-        ora = po.Composer() if name not in WIDGET_ROWS else None
+        ora = po.Composer()
         build(dev, ora, call, 200 + i)
         assert dev.refresh_stats() == (rows, 0, True), (name, dev.refresh_stats())
-        if ora is not None:
-            same(dev, ora)
+        same(dev, ora)
+        if name not in WIDGET_ROWS:
             assert dev.check() == ora.check(), name
         else:
-            assert dev.check() == -1 and dev.circuit_size() == 3 + rows, name
+            assert dev.check() == widgets_of(ora).first_bad(ora) == -1 and dev.circuit_size() == 3 + rows, name
+            assert np.array_equal(dev.materialize()["q_range"].cpu().numpy().view(np.uint64), widgets_of(ora).q_range_column(ora)), name
         dev.clear_witness()
         other, other_call = SIGNED_APPENDS[(i + 1) % len(SIGNED_APPENDS)]
         build(dev, None, other_call, 300 + i)

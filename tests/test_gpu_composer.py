@@ -9,6 +9,7 @@ import torch
 import plonk_gadgets_amd as pg
 from plonk_gadgets_amd import synth
 from tests.refcases import MAX_BOUND_CASES, MAYBE_EQUAL_CASES, RANGE_CHECK_CASES, fits_trim_degree
+from tests.widget_programs import WIDGET_SEEDS, assert_device_equals_oracle, run_widget_program
 
 pytestmark = pytest.mark.gpu
 
@@ -883,6 +884,24 @@ def test_fuzz_composer_programs(engine, seed):
             assert torch.equal(m[wname + "_value"], cols.var_values[getattr(cols, wname)[:n]]), wname
     except AssertionError as e:
         raise AssertionError(f"seed {seed}, program {log}: {e}")
+
+
+# run_fuzz_program's operation list stays what it is (three files replay its seeds' programs): range_check_ragged_batch and the five
+# widget calls are in its sibling, run_widget_program(dev, ora, seed, wit_seed=None, steps=30) of tests/widget_programs.py
+@pytest.mark.parametrize("seed", WIDGET_SEEDS)
+def test_fuzz_widget_programs(engine, seed):
+    """random programs of 30 operations with range_gate / interval_gate calls among batched gadgets and gate batches
+    (tests/widget_programs.py), the widgets replayed on the oracle row for row (tests/widget_oracle.py): same columns, same first
+    failing row -- arithmetic or widget --, same q_range, same sigma at both sizes and through the sparse list's second pass.
+    (Widget rows between footprints that would otherwise join, range segments that merge across calls and across the two gadgets,
+    witnesses that are results of earlier batched gadgets, one Variable under many items, gaps of thousands of rows.)"""
+    dev = pg.StandardComposer(engine, 1 << 14, 1 << 14)
+    dev.auto_grow()
+    both = run_widget_program(dev, None, seed)
+    try:
+        assert_device_equals_oracle(both)
+    except AssertionError as e:
+        raise AssertionError(f"seed {seed}, program {[c[:3] for c in both.log]}: {e}")
 
 
 def test_spread_columns_keeps_the_circuit(engine):

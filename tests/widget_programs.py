@@ -1,0 +1,407 @@
+"""TEST INFRASTRUCTURE: composer programs with range_gate / interval_gate rows in them, made call for call on the device composer
+and on the C oracle's (the widgets through tests/widget_oracle.py), and what is then asserted of the two.
+
+Both(dev, ora) makes one call on both sides, takes every value it needs from the oracle and returns Variables as Python integers;
+dev = None runs the oracle side alone (no GPU, no torch).  assert_device_equals_oracle is the list of DESIGN section 3.19 "Tests":
+columns, check(), q_range, wire values, sigma at the padded size and at n, sigma through the sparse list's second pass, and the
+size-independent properties of sigma.  run_widget_program is the random program of tests/test_gpu_composer.py's
+test_fuzz_widget_programs."""
+import ctypes as C
+import random
+
+import numpy as np
+
+from oracle import pyoracle as po
+from tests import interval_gate_model as im
+from tests import range_gate_model as m
+from tests import widget_oracle as wo
+
+R = m.R
+F = wo.fr_of
+
+
+def scalars(xs):
+    return np.array([po.limbs(F(x)) for x in xs], dtype=np.uint64).reshape(-1, 4)
+
+
+class Both:
+    def __init__(self, dev, ora=None):
+        self.dev, self.ora, self.wid = dev, ora if ora is not None else po.Composer(), wo.Widgets()
+        self.log = []            # (call, items, num_bits or None, first row, rows)
+        if dev is not None:
+            import plonk_gadgets_amd as pg
+            self.S = pg.BlsScalar.from_int
+
+    # -- plumbing ---------------------------------------------------------------------------------------------------------------
+    def t(self, xs):
+        import torch
+        return torch.from_numpy(np.ascontiguousarray(scalars(xs)).view(np.int64)).to("cuda:0")
+
+    def tv(self, xs):
+        import torch
+        return torch.tensor([int(x) for x in xs], dtype=torch.int64, device="cuda:0")
+
+    @property
+    def zero_var(self):
+        return int(self.ora.L.composer_zero_var(self.ora.c))
+
+    def value(self, var):
+        return wo.int_of(self.ora.L.composer_value(self.ora.c, int(var)).l)
+
+    def _same_vars(self, r, o):
+        o = [int(x) for x in o]
+        if self.dev is not None:
+            assert r.cpu().numpy().view(np.uint64).reshape(-1).tolist() == o
+        return o
+
+    def _logged(self, name, items, num_bits, n0):
+        self.log.append((name, items, num_bits, n0, self.ora.n - n0))
+        if self.dev is not None:
+            assert self.dev.circuit_size() == self.ora.n and self.dev.num_variables() == self.ora.num_vars, name
+
+    # -- calls the oracle has ---------------------------------------------------------------------------------------------------
+    def add_input_batch(self, values):
+        first = self.ora.num_vars
+        for v in values:
+            self.ora.allocate(po.limbs(F(v)))
+        if self.dev is not None and len(values):
+            assert self.dev.add_input_batch(self.t(values)) == first
+        return list(range(first, first + len(values)))
+
+    def range_check_batch(self, mn, mx, values):
+        n0 = self.ora.n
+        r = self.dev.range_check_batch(self.S(mn), self.S(mx), self.t(values)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.range_check(self.ora.c, F(mn), F(mx), self.ora.allocate(po.limbs(F(v)))) for v in values])
+        self._logged("range_check_batch", len(values), None, n0)
+        return o
+
+    def range_check_ragged_batch(self, mins, maxs, values):
+        n0 = self.ora.n
+        r = self.dev.range_check_ragged_batch(self.t(mins), self.t(maxs), self.t(values))[0] if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.range_check(self.ora.c, F(lo), F(hi), self.ora.allocate(po.limbs(F(v))))
+                                for lo, hi, v in zip(mins, maxs, values)])
+        self._logged("range_check_ragged_batch", len(values), None, n0)
+        return o
+
+    def max_bound_ragged_batch(self, bounds, values):
+        n0 = self.ora.n
+        r = self.dev.max_bound_ragged_batch(self.t(bounds), self.t(values))[0] if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.max_bound(self.ora.c, F(b), self.ora.allocate(po.limbs(F(v))), None)
+                                for b, v in zip(bounds, values)])
+        self._logged("max_bound_ragged_batch", len(values), None, n0)
+        return o
+
+    def conditionally_select_zero_batch(self, xs, selects):
+        n0 = self.ora.n
+        r = self.dev.conditionally_select_zero_batch(self.tv(xs), self.tv(selects)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.conditionally_select_zero(self.ora.c, a, b) for a, b in zip(xs, selects)])
+        self._logged("conditionally_select_zero_batch", len(xs), None, n0)
+        return o
+
+    def maybe_equal_batch(self, a_vars, b_vars):
+        n0 = self.ora.n
+        r = self.dev.maybe_equal_batch(self.tv(a_vars), self.tv(b_vars)) if self.dev is not None else None
+        L, c = self.ora.L, self.ora.c
+        o = self._same_vars(r, [L.maybe_equal(c, po.AllocatedScalar(a, L.composer_value(c, a)), po.AllocatedScalar(b, L.composer_value(c, b)))
+                                for a, b in zip(a_vars, b_vars)])
+        self._logged("maybe_equal_batch", len(a_vars), None, n0)
+        return o
+
+    def scalar_mix_batch(self, v, y, s, a, b):
+        """-> ([select_one result, maybe_equal result] per item, error count); an item whose v is 0 stops at is_non_zero's error"""
+        n0 = self.ora.n
+        ora = self.ora
+        o, oe = [], []
+        for i in range(len(v)):
+            vv, yy, ss = (ora.add_input(po.limbs(F(x[i]))) for x in (v, y, s))
+            aa, bb = ora.allocate(po.limbs(F(a[i]))), ora.allocate(po.limbs(F(b[i])))
+            oe.append(int(ora.L.is_non_zero(ora.c, vv, F(v[i]))))
+            o.append([int(ora.L.conditionally_select_one(ora.c, yy, ss)), int(ora.L.maybe_equal(ora.c, aa, bb))])
+        if self.dev is not None:
+            r, err, nerr = self.dev.scalar_mix_batch(*[self.t(x) for x in (v, y, s, a, b)])
+            assert r.cpu().numpy().view(np.uint64).tolist() == o and err.cpu().numpy().tolist() == oe and nerr == sum(oe)
+        self._logged("scalar_mix_batch", len(v), None, n0)
+        return o, sum(oe)
+
+    def add_batch(self, q_l, a_vars, q_r, b_vars, q_c):
+        n0 = self.ora.n
+        r = self.dev.add_batch(self.S(q_l), self.tv(a_vars), self.S(q_r), self.tv(b_vars), self.S(q_c)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.composer_add(self.ora.c, F(q_l), a, F(q_r), b, F(q_c), None) for a, b in zip(a_vars, b_vars)])
+        self._logged("add_batch", len(a_vars), None, n0)
+        return o
+
+    def mul_batch(self, q_m, a_vars, b_vars, q_c):
+        n0 = self.ora.n
+        r = self.dev.mul_batch(self.S(q_m), self.tv(a_vars), self.tv(b_vars), self.S(q_c)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.composer_mul(self.ora.c, F(q_m), a, b, F(q_c), None) for a, b in zip(a_vars, b_vars)])
+        self._logged("mul_batch", len(a_vars), None, n0)
+        return o
+
+    def poly_gate_batch(self, a_vars, b_vars, c_vars, q):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.poly_gate_batch(self.tv(a_vars), self.tv(b_vars), self.tv(c_vars), *[self.S(x) for x in q])
+        for a, b, c3 in zip(a_vars, b_vars, c_vars):
+            self.ora.L.composer_poly_gate(self.ora.c, a, b, c3, *[F(x) for x in q], None)
+        self._logged("poly_gate_batch", len(a_vars), None, n0)
+
+    def constrain_to_constant(self, var, constant):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.constrain_to_constant(int(var), self.S(constant), None)
+        self.ora.L.composer_constrain_to_constant(self.ora.c, int(var), F(constant), None)
+        self._logged("constrain_to_constant", 1, None, n0)
+
+    # -- the widgets ------------------------------------------------------------------------------------------------------------
+    def range_gate(self, w, num_bits):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.range_gate(int(w), num_bits)
+        self.wid.range_gate(self.ora, w, num_bits)
+        self._logged("range_gate", 1, num_bits, n0)
+
+    def range_gate_batch(self, ws, num_bits):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.range_gate_batch(self.tv(ws), num_bits)
+        self.wid.range_gate_batch(self.ora, ws, num_bits)
+        self._logged("range_gate_batch", len(ws), num_bits, n0)
+
+    def interval_gate(self, w, lo, hi, num_bits):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.interval_gate(int(w), self.S(lo), self.S(hi), num_bits)
+        self.wid.interval_gate(self.ora, w, lo, hi, num_bits)
+        self._logged("interval_gate", 1, num_bits, n0)
+
+    def interval_gate_batch(self, ws, lo, hi, num_bits):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.interval_gate_batch(self.tv(ws), self.S(lo), self.S(hi), num_bits)
+        self.wid.interval_gate_batch(self.ora, ws, lo, hi, num_bits)
+        self._logged("interval_gate_batch", len(ws), num_bits, n0)
+
+    def interval_gate_ragged_batch(self, ws, los, his, num_bits):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.interval_gate_ragged_batch(self.tv(ws), self.t(los), self.t(his), num_bits)
+        self.wid.interval_gate_ragged_batch(self.ora, ws, los, his, num_bits)
+        self._logged("interval_gate_ragged_batch", len(ws), num_bits, n0)
+
+    def first_bad(self):
+        return self.wid.first_bad(self.ora)
+
+
+def assert_sigma_equal(got, exp, what):
+    """a mismatch is reported as wire / gate / got / expected (position = wire * padded + gate)"""
+    if not np.array_equal(got, exp):
+        w, g = np.argwhere(got != exp)[0]
+        raise AssertionError(f"sigma ({what}) differs first at wire {w}, gate {g}: {got[w, g]} != {exp[w, g]} "
+                             f"({int((got != exp).sum())} positions differ)")
+
+
+def assert_device_equals_oracle(both):
+    """everything the oracle can say of the circuit, asked of the device composer"""
+    import torch
+    import test_gpu_composer as tc
+    from plonk_gadgets_amd import _lib
+    dev, ora, wid = both.dev, both.ora, both.wid
+    tc.same(dev, ora)
+    assert dev.check() == wid.first_bad(ora)
+    n = dev.circuit_size()
+    # q_range: materialised alone into a buffer with a sentinel row behind it, and with every other column
+    alone = torch.full((n + 1, 4), -1, dtype=torch.int64, device="cuda:0")
+    assert dev._lib.pg_composer_materialize(dev._h, C.byref(_lib.FullColumnsC(q_range=alone.data_ptr()))) == 0
+    exp_q = wid.q_range_column(ora)
+    got_q = alone[:-1].cpu().numpy().view(np.uint64)
+    if not np.array_equal(got_q, exp_q):
+        row = int(np.argwhere((got_q != exp_q).any(axis=1))[0])
+        raise AssertionError(f"q_range differs first at row {row}: {got_q[row].tolist()} != {exp_q[row].tolist()}")
+    assert (alone[-1] == -1).all()
+    mat, cols = dev.materialize(), dev.device_columns()
+    assert np.array_equal(mat["q_range"].cpu().numpy().view(np.uint64), exp_q)
+    for wname in ("w_l", "w_r", "w_o"):
+        w = getattr(cols, wname)[:n]
+        expv, gotv = cols.var_values[w], mat[wname + "_value"]
+        if not torch.equal(gotv, expv):
+            bad = int((gotv != expv).any(dim=1).nonzero()[0])
+            raise AssertionError(f"{wname}_value differs first at row {bad} (Variable {int(w[bad])})")
+    del cols
+    padded = 1 << (n - 1).bit_length()
+    exp_sigma = ora.sigma(padded)
+    assert_sigma_equal(dev.permutation(padded).cpu().numpy().view(np.uint64), exp_sigma, f"padded to {padded}")
+    assert_sigma_equal(dev.permutation(n).cpu().numpy().view(np.uint64), ora.sigma(n), f"unpadded, n = {n}")
+    dev.permutation_reserve(16)   # the sparse list far too short: the pass reports its size and runs a second time
+    try:
+        assert_sigma_equal(dev.permutation(padded).cpu().numpy().view(np.uint64), exp_sigma, "sparse list reserved for 16")
+    finally:
+        dev.permutation_reserve(0)
+    tc._sigma_properties(dev, padded)
+
+
+# ---- the random program -------------------------------------------------------------------------------------------------------
+WIDGET_CALLS = ("range_gate", "range_gate_batch", "interval_gate", "interval_gate_batch", "interval_gate_ragged_batch")
+OPERATIONS = ("add_input_batch", "range_check_batch", "max_bound_ragged_batch", "range_check_ragged_batch",
+              "conditionally_select_zero_batch", "maybe_equal_batch", "scalar_mix_batch", "add_batch", "poly_gate_batch",
+              "constrain_to_constant") + WIDGET_CALLS * 2
+WIDTHS = tuple(sorted(set(m.NUM_BITS) | set(im.NUM_BITS) | {16}))
+UNKNOWN = (0, R - 1)
+# the programs of test_fuzz_widget_programs, chosen against the oracle (tests/test_widget_programs.py says what they reach); those
+# above 100 have batches of 400 .. 2500 for the small items and the widgets
+WIDGET_SEEDS = (1, 5, 9, 12, 13, 19, 20, 24, 27, 28, 103, 106)
+SMALL = 1 << 250                 # sums and products of two values below this stay below r
+
+
+def run_widget_program(dev, ora, seed, wit_seed=None, steps=30):
+    """a random program of `steps` operations (OPERATIONS) on the device composer and, call for call, on the oracle's.  Everything
+    PUBLIC comes from `seed`: operations, sizes, widths, bounds, selectors, constants, which earlier Variables a call refers to, and
+    where a failure is planted; the WITNESS scalars from `wit_seed` (default: seed).  The program knows of every Variable a public
+    interval [lo, hi] that holds its value whatever the witnesses (an input drawn below 2^b, a gadget's 0 / 1 result, a sum of two
+    such), and a widget takes earlier Variables only where that interval lies inside its own: every widget witness is in range by
+    construction, and check() is -1 unless the program plants a failure.  With probability 1/2 it does: a widget witness out of range
+    (by one, or r - 1), a constrain_to_constant to a wrong constant, or both, at random steps.  -> Both (log, ora, wid)"""
+    rng = random.Random(seed)
+    wrng = random.Random(seed if wit_seed is None else wit_seed)
+    both = Both(dev, ora)
+    big = seed > 100
+    known = {0: (0, 0)}          # Variable -> public interval of its value
+    constants = {0: 0}           # Variable -> public value (inputs every build allocates with the same scalar)
+    results = set()              # result Variables of batched gadgets
+    both.gadget_witnesses = 0    # how many widget items took one of them
+
+    def learn(vs, lo, hi, gadget=True):
+        for v in vs:
+            known[v] = (lo, hi)
+        if gadget:
+            results.update(vs)
+
+    def drawn(lo, hi):
+        """a witness in [lo, hi], the ends among them"""
+        return wrng.choice([lo, hi, wrng.randrange(lo, hi + 1), wrng.randrange(lo, hi + 1)])
+
+    def earlier(k, inside=None):
+        """k earlier Variables; inside = (lo, hi): only such as are publicly known to lie in it"""
+        if inside is None:
+            nv = both.ora.num_vars
+            return [rng.randrange(nv) for _ in range(k)]
+        if inside not in fits:
+            fits[inside] = [v for v, (lo, hi) in known.items() if inside[0] <= lo and hi <= inside[1]]
+        return [rng.choice(fits[inside]) for _ in range(k)] if fits[inside] else []
+
+    fits = {}
+    plant = rng.choice([None, None, None, "widget", "constant", "both"])
+    plant_widget = rng.randrange(steps) if plant in ("widget", "both") else None      # the first widget call from this step on
+    plant_constant = rng.randrange(steps) if plant in ("constant", "both") else None
+    # inputs of public value, the same in every build
+    cvals = [rng.choice([0, 1, 2, 3, rng.randrange(1 << 16), rng.randrange(1 << 60)]) for _ in range(6)]
+    for v, x in zip(both.add_input_batch(cvals), cvals):
+        constants[v] = x
+        known[v] = (x, x)
+    for step in range(steps):
+        op = rng.choice(OPERATIONS)
+        fits = {}                # earlier()'s candidates per interval, as known at the start of the step
+        k = rng.randrange(1, 40)
+        small_items = op not in ("range_check_batch", "max_bound_ragged_batch", "range_check_ragged_batch", "constrain_to_constant",
+                                 "range_gate", "interval_gate")
+        if big and small_items:
+            k = rng.randrange(400, 2500)  # thousands of rows in one gap, many groups per segment
+        if step == plant_constant:
+            v = rng.choice(sorted(constants))
+            both.constrain_to_constant(v, (constants[v] + rng.choice([1, R - 1])) % R)
+        if op == "add_input_batch":
+            b = rng.choice(WIDTHS)
+            learn(both.add_input_batch([drawn(0, 2**b - 1) for _ in range(k)]), 0, 2**b - 1, gadget=False)
+        elif op == "range_check_batch":
+            mx = rng.randrange(2, 1 << rng.randrange(2, 40))
+            mn = rng.randrange(0, mx)
+            learn(both.range_check_batch(mn, mx, [drawn(0, 2 * mx) for _ in range(k)]), 0, 1)
+        elif op == "max_bound_ragged_batch":
+            bounds = [rng.randrange(1, 1 << rng.randrange(1, 100)) for _ in range(k)]
+            learn(both.max_bound_ragged_batch(bounds, [drawn(0, 2 * b) for b in bounds]), 0, 1)
+        elif op == "range_check_ragged_batch":
+            maxs = [rng.randrange(2, 1 << rng.randrange(2, 60)) for _ in range(k)]
+            mins = [rng.randrange(0, mx) for mx in maxs]
+            learn(both.range_check_ragged_batch(mins, maxs, [drawn(0, 2 * mx) for mx in maxs]), 0, 1)
+        elif op == "conditionally_select_zero_batch":
+            xs, sel = earlier(k), earlier(k)
+            res = both.conditionally_select_zero_batch(xs, sel)
+            for r, x, s in zip(res, xs, sel):   # the result is x * select
+                xh, sh = known.get(x, UNKNOWN)[1], known.get(s, UNKNOWN)[1]
+                known[r] = (0, xh * sh) if xh < SMALL and sh < 4 else UNKNOWN
+            results.update(res)
+        elif op == "maybe_equal_batch":
+            learn(both.maybe_equal_batch(earlier(k), earlier(k)), 0, 1)
+        elif op == "scalar_mix_batch":
+            v = [wrng.randrange(1, R) for _ in range(k)]                       # (never 0: no item stops at its error)
+            y, s, a, b = ([wrng.choice([0, 1, wrng.randrange(R)]) for _ in range(k)] for _ in range(4))
+            res, _ = both.scalar_mix_batch(v, y, s, a, b)
+            learn([r[1] for r in res], 0, 1)                                    # maybe_equal's; select_one's may be anything
+        elif op == "add_batch":
+            c = rng.choice([0, 1, rng.randrange(1 << 20)])
+            a, b = earlier(k, (0, SMALL)) or [0] * k, earlier(k, (0, SMALL)) or [0] * k
+            res = both.add_batch(1, a, 1, b, c)
+            for r, x, y in zip(res, a, b):
+                known[r] = (known[x][0] + known[y][0] + c, known[x][1] + known[y][1] + c)
+            results.update(res)
+        elif op == "poly_gate_batch":
+            a, c3 = earlier(k), earlier(k)
+            x = rng.choice([0, 1, rng.randrange(R)])
+            both.poly_gate_batch(a, a, c3, [0, x, (R - x) % R, 0, 0])          # x a - x a = 0 whatever a holds
+        elif op == "constrain_to_constant":
+            v = rng.choice(sorted(constants))
+            both.constrain_to_constant(v, constants[v])
+        else:
+            num_bits = rng.choice([b for b in WIDTHS if b <= (16 if big and small_items else 254)])
+            interval = op.startswith("interval")
+            if interval:
+                num_bits = min(num_bits, 252)
+            if op in ("range_gate", "interval_gate"):
+                k = rng.randrange(1, 4)        # that many single calls
+            top = 2**num_bits - 1
+            # the bounds, item by item (one pair for all but the ragged call)
+            if not interval:
+                bounds = [(0, top)] * k
+            else:
+                def pair():
+                    lo = rng.choice([0, 0, rng.randrange(1 << 16), rng.randrange(R - top)])
+                    return lo, lo + rng.choice([top, rng.randrange(top + 1)])
+                pairs = [pair() for _ in range(min(k, 6))]      # (a pair per item, of a few kinds)
+                bounds = [rng.choice(pairs) for _ in range(k)] if op == "interval_gate_ragged_batch" else pairs[:1] * k
+            # the witnesses: an earlier Variable known to be inside, the previous item's again, or a fresh input
+            kinds = [rng.choice(["earlier", "earlier", "repeat", "fresh"]) for _ in range(k)]
+            bad_item = rng.randrange(k) if plant_widget is not None and step >= plant_widget else None
+            ws, fresh = [], []
+            for i, (kind, (lo, hi)) in enumerate(zip(kinds, bounds)):
+                cand = earlier(1, (lo, hi)) if kind == "earlier" and i != bad_item else []
+                if i == bad_item:
+                    out = [x for x in ((hi + 1) % R, (lo - 1) % R, R - 1) if not lo <= x <= hi]
+                    fresh.append(rng.choice(out))
+                    ws.append(None)
+                elif cand:
+                    ws.append(cand[0])
+                    both.gadget_witnesses += cand[0] in results
+                elif kind == "repeat" and i and ws[-1] is not None and lo <= known[ws[-1]][0] and known[ws[-1]][1] <= hi:
+                    ws.append(ws[-1])
+                else:
+                    fresh.append(drawn(lo, hi))
+                    ws.append(None)
+            if bad_item is not None:
+                plant_widget = None
+            new = iter(both.add_input_batch(fresh))
+            for i, w in enumerate(ws):
+                if w is None:
+                    ws[i] = next(new)
+                    known[ws[i]] = bounds[i] if i != bad_item else UNKNOWN
+            if op == "range_gate":
+                for w in ws:
+                    both.range_gate(w, num_bits)
+            elif op == "range_gate_batch":
+                both.range_gate_batch(ws, num_bits)
+            elif op == "interval_gate":
+                for w, (lo, hi) in zip(ws, bounds):
+                    both.interval_gate(w, lo, hi, num_bits)
+            elif op == "interval_gate_batch":
+                both.interval_gate_batch(ws, bounds[0][0], bounds[0][1], num_bits)
+            else:
+                both.interval_gate_ragged_batch(ws, [b[0] for b in bounds], [b[1] for b in bounds], num_bits)
+    return both
