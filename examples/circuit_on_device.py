@@ -5,7 +5,9 @@
 
 The reference's loop
     for w in witnesses { let a = AllocatedScalar::allocate(composer, w); results.push(range_check(composer, min, max, a)); }
-is one batched append on the device-resident composer; single calls with the reference's signatures mix in freely.
+is one batched append on the device-resident composer; single calls with the reference's signatures mix in freely.  Then a
+per-account limit check: every amount in 16 bits, limit - (the account's amounts) by ONE weighted_sum_ragged_batch over ragged
+accounts, and the headrooms in 16 bits again.
 """
 import os
 import sys
@@ -45,6 +47,25 @@ def main():
     t_build = time.perf_counter() - t
     n = composer.circuit_size()
     assert composer.check() == -1                          # every row satisfies its gate equation
+    built_rows = n
+
+    # amounts against per-account limits: accounts of 2 .. 9 transfers of < 2^12 each, every limit 2^16 - 1
+    accounts = max(1, batch // 8)
+    sizes = torch.randint(2, 10, (accounts,), device="cuda:0")
+    seg_off = torch.cat([torch.zeros(1, dtype=torch.int64, device="cuda:0"), torch.cumsum(sizes, 0)])
+    transfers = int(seg_off[-1])
+    small = lambda xs: torch.from_numpy(synth.scalars_from_ints(xs).view(np.int64)).to("cuda:0")
+    amounts = small(range(1 << 12))[torch.randint(0, 1 << 12, (transfers,), device="cuda:0")].contiguous()
+    first_amount = composer.add_input_batch(amounts)
+    amount_vars = torch.arange(first_amount, first_amount + transfers, dtype=torch.int64, device="cuda:0")
+    composer.range_gate_batch(amount_vars, 16)                                   # every amount < 2^16
+    minus_one, limit = small([synth.Q - 1]), small([2**16 - 1])
+    headroom = composer.weighted_sum_ragged_batch(amount_vars, seg_off, minus_one.repeat(transfers, 1).contiguous(),
+                                                  limit.repeat(accounts, 1).contiguous())   # limit - sum of the account's amounts
+    composer.range_gate_batch(headroom, 16)                                      # ... is not negative
+    n = composer.circuit_size()
+    assert composer.check() == -1
+    print("%d transfers of %d accounts under their limits: %d rows" % (transfers, accounts, n))
 
     t = time.perf_counter()
     padded = 1 << (n - 1).bit_length()
@@ -52,8 +73,8 @@ def main():
     sigma = composer.permutation(padded)                   # copy permutation, int64[4, padded]
     torch.cuda.synchronize()
     t_ready = time.perf_counter() - t
-    print("%d witnesses -> %d rows, %d variables: built in %.2f ms (%.3g constraints/s), prover-ready in another %.2f ms"
-          % (batch, n, composer.num_variables(), t_build * 1e3, n / t_build, t_ready * 1e3))
+    print("%d witnesses and the limit check -> %d rows, %d variables: the witnesses' rows built in %.2f ms (%.3g constraints/s), prover-ready in another %.2f ms"
+          % (batch, n, composer.num_variables(), t_build * 1e3, built_rows / t_build, t_ready * 1e3))
     assert full["q_arith"].shape == (n, 4) and sigma.shape == (4, padded)
 
 

@@ -275,6 +275,13 @@ inline void interval_gate(StandardComposer &c, const pg_variable *d_witness_var,
                           uint64_t batch) {
     pg_throw(pg_composer_interval_gate_ragged_batch(c.h, d_witness_var, d_min, d_max, num_bits, batch), "Batched::interval_gate (ragged)");
 }
+// result[s] = d_constant[s] + sum over t in d_seg_off[s] .. d_seg_off[s + 1] - 1 of d_coeff[t] * d_term_var[t], as the chain of composer.add calls
+// (every segment >= 2 terms; d_coeff / d_constant / d_result_vars may be NULL: all 1 / all 0 / not wanted): terms - segments rows
+inline void weighted_sum(StandardComposer &c, const pg_variable *d_term_var, const uint64_t *d_seg_off, const pg_scalar *d_coeff,
+                         const pg_scalar *d_constant, uint64_t terms, uint64_t segments, pg_variable *d_result_vars) {
+    pg_throw(pg_composer_weighted_sum_ragged_batch(c.h, d_term_var, d_seg_off, d_coeff, d_constant, terms, segments, d_result_vars),
+             "Batched::weighted_sum (ragged)");
+}
 // Ok, or Error::NonExistingInverse when some item's value was zero (all items are appended either way, the failing
 // ones as far as the reference gets before it returns the error); *err_count = how many
 inline Result is_non_zero(StandardComposer &c, const pg_variable *d_var, uint64_t batch, uint8_t *d_err_mask, uint64_t *err_count) {

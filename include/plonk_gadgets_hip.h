@@ -505,6 +505,34 @@ pg_status pg_composer_mul_batch(pg_composer *c, const pg_scalar *q_m, const pg_v
 pg_status pg_composer_constrain_to_constant_batch(pg_composer *c, const pg_variable *d_a, const pg_scalar *constant, uint64_t batch);
 pg_status pg_composer_boolean_gate_batch(pg_composer *c, const pg_variable *d_a, uint64_t batch);
 
+/* weighted_sum_ragged_batch: result[s] = k[s] + sum over the terms t of segment s of c[t] * value(x[t]), the loop
+ *   for s in segments:                  terms b = d_seg_off[s] .. e = d_seg_off[s + 1] - 1, m = e - b + 1 >= 2
+ *       acc = composer.add((c[b], x[b]), (c[b+1], x[b+1]), k[s], None)
+ *       for t in b+2 .. e: acc = composer.add((1, acc), (c[t], x[t]), 0, None)
+ *       result[s] = acc
+ * on EXISTING Variables x = d_term_var, their assignments read from the composer's own table.  With n0 rows and v0 Variables before
+ * the call, term t with b < t <= e owns row n0 + (t - s - 1) and creates Variable v0 + (t - s - 1) (a segment's first term owns
+ * neither): the call owns terms - segments rows and as many Variables, and result[s] = v0 + d_seg_off[s + 1] - s - 2.
+ *   t = b+1:  wires (x[b], x[b+1], new)      q_m = 0  q_l = c[b]  q_r = c[b+1]  q_o = -1  q_c = k[s]
+ *   t > b+1:  wires (new - 1, x[t], new)     q_m = 0  q_l = 1     q_r = c[t]    q_o = -1  q_c = 0
+ * and the new Variable holds k[s] + sum_{i = b .. t} c[i] value(x[i]).  d_coeff [terms] or NULL: every coefficient 1; d_constant
+ * [segments] or NULL: every constant 0 (Montgomery form, like every pg_scalar); d_result_vars [segments] or NULL.
+ * Preconditions, else PG_ERR_INVALID_ARGUMENT with nothing appended: d_term_var and d_seg_off not NULL and 8-byte aligned, the
+ * scalar arrays 16-byte aligned; terms < 2^32; every term a Variable of this composer; d_seg_off[0] == 0, d_seg_off[segments] ==
+ * terms and every segment of at least 2 terms; every coefficient and constant reduced.  The arrays are validated on the device, in
+ * one host synchronisation, before any entry of d_seg_off is used as an index; the message names the first offending segment,
+ * coefficient or constant.  segments == 0 (terms must then be 0): PG_OK, nothing appended.
+ * A one-term "sum" is x itself (or pg_composer_add_batch with a second operand): a caller who needs one in a ragged call pads the
+ * segment with the composer's zero_var, which adds 0 whatever its coefficient.
+ * The rows are ordinary arithmetic rows.  After pg_composer_clear_witness the same call -- same four arrays' contents, same place --
+ * finds its rows and writes the assignments only. */
+pg_status pg_composer_weighted_sum_ragged_batch(pg_composer *c, const pg_variable *d_term_var, const uint64_t *d_seg_off,
+                                                const pg_scalar *d_coeff, const pg_scalar *d_constant, uint64_t terms, uint64_t segments,
+                                                pg_variable *d_result_vars);
+/* host only: the terms a workgroup takes per step (a power of two) and the tiles the carry launch scans at a time; a call of
+ * more than tile_terms terms carries sums between tiles, one of more than tile_terms * tiles_per_carry_pass between passes */
+pg_status pg_weighted_sum_geometry(uint32_t *tile_terms, uint32_t *tiles_per_carry_pass);
+
 /* ragged batched appends: the composer plans the call itself (one host synchronisation for the totals), keeps the
  * per-item offsets for the permutation, and emits.
  *   max_bound_ragged: for i { allocate(d_witness[i]); max_bound(composer, d_max_range[i], w) } -- one public bound per

@@ -27,6 +27,7 @@
 #include "scalar_gadgets.hpp"
 #include "composer.hpp"
 #include "interval_gate.hpp"
+#include "weighted_sum.hpp"
 #include "permutation.hpp"
 #include "materialize.hpp"
 #include "permutation_product.hpp"

@@ -29,6 +29,7 @@ struct pg_composer {
     std::vector<pg::PermSeg> segs;
     Scratch perm_small, perm_big, val_ws;  // val_ws: gathered assignments of batched calls
     Scratch perm_pieces;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
+    Scratch wsum_ws;  // pg_composer_weighted_sum_ragged_batch: its tiles' aggregates and carries (weighted_sum.hpp)
     std::vector<RaggedBuffers> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
     Pinned h_total;  // 8 words: what a call reads back (made by pg_composer_create)
     uint64_t *totals() const { return h_total.as<uint64_t>(); }
@@ -166,7 +167,8 @@ enum class SigKind : uint64_t {
     MAX_BOUND_RAGGED_BATCH = 31,     // pg_composer_max_bound_ragged_batch (it signed with 27, range_gate's, until the kinds had names)
     DECOMPOSITION = 43,              // pg_scalar_decomposition_gadget
     INTERVAL_GATE_BATCH = 61,        // pg_composer_interval_gate_batch, pg_composer_interval_gate (a batch of one)
-    INTERVAL_GATE_RAGGED_BATCH = 62  // pg_composer_interval_gate_ragged_batch
+    INTERVAL_GATE_RAGGED_BATCH = 62,  // pg_composer_interval_gate_ragged_batch
+    WEIGHTED_SUM_RAGGED_BATCH = 63    // pg_composer_weighted_sum_ragged_batch
 };
 // kind: which call; b0, b1: its public scalars; extra: a public integer; dg: the digest of the device arrays its rows depend on
 pg_composer::Sig gadget_sig(const pg_composer *c, SigKind kind, const pg::Fr &b0, const pg::Fr &b1, uint64_t batch, uint64_t extra,
@@ -1294,6 +1296,129 @@ pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t n
     PG_TRY(range_num_bits(num_bits));
     PG_TRY(stage_variable(c, witness));
     return range_gate_batch(c, c->stage_words(), num_bits, 1);
+}
+
+}  // extern "C"
+
+namespace {
+// The device arrays of a weighted sum in ONE host synchronisation (the one check_var_arrays pays): the terms' maximum and digest, and,
+// from one pass over seg_off, the coefficients and the constants (weighted_sum_check_kernel), their digest and the first entry of
+// each that violates a precondition.  Nothing has used an entry of seg_off as an index before this returns PG_OK.
+pg_status check_weighted_sum_arrays(pg_composer *c, const pg_variable *d_term_var, const uint64_t *d_seg_off, const pg_scalar *d_coeff,
+                                    const pg_scalar *d_constant, uint64_t terms, uint64_t segments, pg_composer::Sig *vars_dg,
+                                    pg_composer::Sig *arrays_dg) {
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    // the staging blob's last eight words: [first bad segment, coefficient, constant | the three arrays' digest | check_var_arrays' three]
+    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 32);
+    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 64, c->stream));
+    PG_HIP_TRY(hipMemsetAsync(d_out, 0xff, 24, c->stream));
+    digest_words(c, d_term_var, terms, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
+    const uint64_t want = (terms + pg::kThreads - 1) / pg::kThreads, few = (uint64_t)c->e->num_cus * 2;
+    hipLaunchKernelGGL(pg::weighted_sum_check_kernel, dim3((uint32_t)(want < few ? want : few)), dim3(pg::kThreads), 0, c->stream, d_seg_off,
+                       reinterpret_cast<const uint4 *>(d_coeff), reinterpret_cast<const uint4 *>(d_constant), terms, segments, d_out);
+    PG_HIP_TRY(hipGetLastError());
+    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 64, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipStreamSynchronize(c->stream));
+    const uint64_t *t = c->totals();
+    if (t[5] >= c->nvars)
+        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(t[5]) + " in a batched append (the composer has " +
+                                                 std::to_string(c->nvars) + ")");
+    if (t[0] != ~0ull)
+        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: d_seg_off must start at 0, end at terms = " + std::to_string(terms) +
+                                                 " and give every segment at least 2 terms; the first offending segment is " +
+                                                 std::to_string(t[0]));
+    if (t[1] != ~0ull)
+        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: coefficient " + std::to_string(t[1]) + " is not reduced below the modulus");
+    if (t[2] != ~0ull)
+        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: constant " + std::to_string(t[2]) + " is not reduced below the modulus");
+    *vars_dg = pg_composer::Sig{t[6], t[7]};
+    *arrays_dg = pg_composer::Sig{t[3], t[4]};
+    return PG_OK;
+}
+
+// the three launches of weighted_sum.hpp on the composer's stream; one tile: the writer alone
+pg_status weighted_sum_launch(pg_composer *c, const pg_variable *d_term_var, const uint64_t *d_seg_off, const pg_scalar *d_coeff,
+                              const pg_scalar *d_constant, const pg_scalar *values, uint64_t terms, uint64_t segments,
+                              const pg_columns *at, pg_variable *d_result_vars, bool values_only) {
+    pg::WeightedSumArgs A{};
+    A.term_var = d_term_var;
+    A.seg_off = d_seg_off;
+    A.val = reinterpret_cast<const uint4 *>(values);
+    A.coeff = reinterpret_cast<const uint4 *>(d_coeff);
+    A.konst = reinterpret_cast<const uint4 *>(d_constant);
+    A.terms = terms;
+    A.segments = segments;
+    A.tiles = (terms + pg::kWsTile - 1) / pg::kWsTile;
+    A.q[0] = reinterpret_cast<uint4 *>(at->q_m);
+    A.q[1] = reinterpret_cast<uint4 *>(at->q_l);
+    A.q[2] = reinterpret_cast<uint4 *>(at->q_r);
+    A.q[3] = reinterpret_cast<uint4 *>(at->q_o);
+    A.q[4] = reinterpret_cast<uint4 *>(at->q_c);
+    A.w[0] = at->w_l;
+    A.w[1] = at->w_r;
+    A.w[2] = at->w_o;
+    A.vars = reinterpret_cast<uint4 *>(at->var_values);
+    A.var_base = c->nvars;
+    A.result_vars = d_result_vars;
+    if (A.tiles > 1) {
+        // per tile: its sum and its carry (32 bytes each), then the flags
+        PG_TRY(perm_reserve(c, c->wsum_ws, A.tiles * (2 * sizeof(pg_scalar) + sizeof(uint32_t))));
+        A.tile_sum = c->wsum_ws.as<uint4>();
+        A.tile_carry = A.tile_sum + 2 * A.tiles;
+        A.tile_flag = reinterpret_cast<uint32_t *>(A.tile_carry + 2 * A.tiles);
+        hipLaunchKernelGGL(pg::weighted_sum_tiles_kernel, dim3((uint32_t)A.tiles), dim3(pg::kThreads), 0, c->stream, A);
+        hipLaunchKernelGGL(pg::weighted_sum_carry_kernel, dim3(1), dim3(pg::kThreads), 0, c->stream, A);
+    }
+    if (values_only) hipLaunchKernelGGL(pg::weighted_sum_write_kernel<false>, dim3((uint32_t)A.tiles), dim3(pg::kThreads), 0, c->stream, A);
+    else hipLaunchKernelGGL(pg::weighted_sum_write_kernel<true>, dim3((uint32_t)A.tiles), dim3(pg::kThreads), 0, c->stream, A);
+    PG_HIP_TRY(hipGetLastError());
+    return PG_OK;
+}
+}  // namespace
+
+extern "C" {
+
+pg_status pg_weighted_sum_geometry(uint32_t *tile_terms, uint32_t *tiles_per_carry_pass) {
+    if (!tile_terms || !tiles_per_carry_pass) return fail(PG_ERR_INVALID_ARGUMENT, "NULL argument");
+    *tile_terms = pg::kWsTile;
+    *tiles_per_carry_pass = pg::kWsCarryPass;
+    return PG_OK;
+}
+
+// The rows leave no footprint (sigma and the wire values take the generic routes).  The rows: the four arrays' contents, with NULL
+// told from present, terms, segments and where the call lands.
+pg_status pg_composer_weighted_sum_ragged_batch(pg_composer *c, const pg_variable *d_term_var, const uint64_t *d_seg_off,
+                                                const pg_scalar *d_coeff, const pg_scalar *d_constant, uint64_t terms, uint64_t segments,
+                                                pg_variable *d_result_vars) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    if (segments == 0) {
+        if (terms) return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: " + std::to_string(terms) + " terms in no segment");
+        return flush(c);
+    }
+    if (terms >> 32) return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: terms must be below 2^32, got " + std::to_string(terms));
+    if (terms == 0)
+        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: every segment needs at least 2 terms; the first offending segment is 0");
+    PG_TRY(check_u64s(d_seg_off, "d_seg_off"));
+    if (d_coeff) PG_TRY(check_scalars(d_coeff, "d_coeff"));
+    if (d_constant) PG_TRY(check_scalars(d_constant, "d_constant"));
+    PG_TRY(check_u64s(d_result_vars, "d_result_vars", true));
+    const uint64_t rows = terms > segments ? terms - segments : 0;  // (terms >= 2 segments once the arrays are checked)
+    pg::Fr b0 = pg::fr_zero();  // what the signature has for the arrays: their digest, and which of the optional ones are there
+    b0.l[2] = (d_coeff ? 1u : 0u) | (d_constant ? 2u : 0u);
+    return var_batch(
+        c, {{d_term_var, "d_term_var"}}, terms, rows, rows,
+        [&](pg_composer::Sig *dg) -> pg_status {
+            pg_composer::Sig arrays;
+            PG_TRY(check_weighted_sum_arrays(c, d_term_var, d_seg_off, d_coeff, d_constant, terms, segments, dg, &arrays));
+            b0.l[0] = arrays.a;
+            b0.l[1] = arrays.b;
+            return PG_OK;
+        },
+        [&](const pg_composer::Sig &dg) { return gadget_sig(c, SigKind::WEIGHTED_SUM_RAGGED_BATCH, b0, pg::fr_zero(), terms, segments, dg); },
+        [&](const pg_columns *at, const pg_scalar *values, bool in_place) {
+            return weighted_sum_launch(c, d_term_var, d_seg_off, d_coeff, d_constant, values, terms, segments, at, d_result_vars, in_place);
+        },
+        [] {});
 }
 
 pg_status pg_composer_conditionally_select_zero_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_select_var,
