@@ -42,40 +42,7 @@ def _opt(pi: BlsScalar | None):
     return C.byref(pi.c) if pi is not None else None
 
 
-class SegmentedAppends:
-    """Appends over ragged SEGMENTS of existing Variables (a result per segment, not per item), which StandardComposer inherits.
-    They stand apart from the class's own *_batch methods, one row group per item, which tests/test_gpu_clear_witness.py lists in
-    one table; what that table checks of a call's signature -- in place on other witnesses, never taken for a neighbour's rows -- is
-    checked for these in tests/test_gpu_weighted_sum.py.  Uses the composer's _lib, _h and _hand_over."""
-
-    def weighted_sum_ragged_batch(self, term_vars: torch.Tensor, seg_off: torch.Tensor, coeffs: torch.Tensor | None = None,
-                                  constants: torch.Tensor | None = None) -> torch.Tensor:
-        """for s: result[s] = constants[s] + sum over t in seg_off[s] .. seg_off[s + 1] - 1 of coeffs[t] * term_vars[t], as the chain
-        add((c, x), (c, x), k), add((1, acc), (c, x), 0), ... on existing Variables (DESIGN section 3.22).  term_vars int64[terms],
-        seg_off int64[segments + 1] (0 first, terms last, every segment of at least 2 terms), coeffs int64[terms, 4] or None (all 1),
-        constants int64[segments, 4] or None (all 0), Montgomery form -> the result Variables int64[segments].  terms - segments rows and
-        new Variables; an array that violates a precondition refuses the whole call and the error names the first offender"""
-        for x in (term_vars, seg_off):
-            assert x.is_cuda and x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous()
-        for x in (coeffs, constants):
-            assert x is None or (x.is_cuda and x.dtype == torch.int64 and x.dim() == 2 and x.shape[1] == 4 and x.is_contiguous())
-        if seg_off.shape[0] < 1:
-            raise ValueError("seg_off needs segments + 1 entries, got none")
-        terms, segments = term_vars.shape[0], seg_off.shape[0] - 1
-        if coeffs is not None and coeffs.shape[0] != terms:
-            raise ValueError(f"term_vars and coeffs differ in length: {terms}, {coeffs.shape[0]}")
-        if constants is not None and constants.shape[0] != segments:
-            raise ValueError(f"seg_off names {segments} segments, constants {constants.shape[0]}")
-        res = torch.empty((segments,), dtype=torch.int64, device=term_vars.device)
-        with self._hand_over():
-            _chk(self._lib.pg_composer_weighted_sum_ragged_batch(self._h, term_vars.data_ptr(), seg_off.data_ptr(),
-                                                                 coeffs.data_ptr() if coeffs is not None else None,
-                                                                 constants.data_ptr() if constants is not None else None, terms, segments,
-                                                                 res.data_ptr()), "pg_composer_weighted_sum_ragged_batch")
-        return res
-
-
-class StandardComposer(SegmentedAppends):
+class StandardComposer:
     """pg_composer: dusk-plonk's StandardComposer slice used by the gadgets, columns resident in HBM."""
 
     def __init__(self, engine: Engine, gate_capacity: int = 1 << 16, var_capacity: int = 1 << 16, with_dummy: bool = True):
@@ -407,6 +374,32 @@ class StandardComposer(SegmentedAppends):
             _chk(self._lib.pg_composer_add_batch(self._h, C.byref(q_l.c), a.data_ptr(), C.byref(q_r.c), b.data_ptr(), C.byref(q_c.c), n,
                                                  out.data_ptr()), "pg_composer_add_batch")
         return out
+
+    def weighted_sum_ragged_batch(self, term_vars: torch.Tensor, seg_off: torch.Tensor, coeffs: torch.Tensor | None = None,
+                                  constants: torch.Tensor | None = None) -> torch.Tensor:
+        """for s: result[s] = constants[s] + sum over t in seg_off[s] .. seg_off[s + 1] - 1 of coeffs[t] * term_vars[t], as the chain
+        add((c, x), (c, x), k), add((1, acc), (c, x), 0), ... on existing Variables (DESIGN section 3.22).  term_vars int64[terms],
+        seg_off int64[segments + 1] (0 first, terms last, every segment of at least 2 terms), coeffs int64[terms, 4] or None (all 1),
+        constants int64[segments, 4] or None (all 0), Montgomery form -> the result Variables int64[segments].  terms - segments rows and
+        new Variables; an array that violates a precondition refuses the whole call and the error names the first offender"""
+        for x in (term_vars, seg_off):
+            assert x.is_cuda and x.dtype == torch.int64 and x.dim() == 1 and x.is_contiguous()
+        for x in (coeffs, constants):
+            assert x is None or (x.is_cuda and x.dtype == torch.int64 and x.dim() == 2 and x.shape[1] == 4 and x.is_contiguous())
+        if seg_off.shape[0] < 1:
+            raise ValueError("seg_off needs segments + 1 entries, got none")
+        terms, segments = term_vars.shape[0], seg_off.shape[0] - 1
+        if coeffs is not None and coeffs.shape[0] != terms:
+            raise ValueError(f"term_vars and coeffs differ in length: {terms}, {coeffs.shape[0]}")
+        if constants is not None and constants.shape[0] != segments:
+            raise ValueError(f"seg_off names {segments} segments, constants {constants.shape[0]}")
+        res = torch.empty((segments,), dtype=torch.int64, device=term_vars.device)
+        with self._hand_over():
+            _chk(self._lib.pg_composer_weighted_sum_ragged_batch(self._h, term_vars.data_ptr(), seg_off.data_ptr(),
+                                                                 coeffs.data_ptr() if coeffs is not None else None,
+                                                                 constants.data_ptr() if constants is not None else None, terms, segments,
+                                                                 res.data_ptr()), "pg_composer_weighted_sum_ragged_batch")
+        return res
 
     def mul_batch(self, q_m: BlsScalar, a, b, q_c: BlsScalar) -> torch.Tensor:
         n = self._vars(a, b)

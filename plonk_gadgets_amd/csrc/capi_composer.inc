@@ -17,8 +17,9 @@ struct pg_composer {
     uint64_t n = 0, nvars = 0, zero_var = 0;
     // the nine columns: separate arrays, or ONE block with the selector columns a stride apart (pg_composer_spread_columns)
     ColumnStore cols;
-    Scratch d_stage;  // 40 words: inputs of single-gadget calls
+    Scratch d_stage;  // a StageBlob: inputs of single-gadget calls
     uint64_t *stage_words() const { return d_stage.as<uint64_t>(); }
+    Scratch d_preflight;  // a pg::Preflight: what the passes over an append's device arrays leave (preflight())
     // public_inputs_sparse_store and the rows with a live fourth wire (host copies; uploaded by check/materialize)
     std::vector<uint64_t> pi_gate;
     std::vector<pg_scalar> pi_val;
@@ -31,7 +32,7 @@ struct pg_composer {
     Scratch perm_pieces;  // pg_composer_permutation: the first item of every piece of a ragged ladder segment's rows
     Scratch wsum_ws;  // pg_composer_weighted_sum_ragged_batch: its tiles' aggregates and carries (weighted_sum.hpp)
     std::vector<RaggedBuffers> ragged;  // device prefix sums / ladder lengths of the ragged calls (referenced by segs)
-    Pinned h_total;  // 8 words: what a call reads back (made by pg_composer_create)
+    Pinned h_total;  // 64 bytes: what a call reads back, a preflight its pg::Preflight (made by pg_composer_create)
     uint64_t *totals() const { return h_total.as<uint64_t>(); }
     uint64_t perm_last_sparse = 0;  // size of the sparse list the last permutation needed
     uint64_t sparse_hint = 0;       // wire positions the batched calls so far are expected to put on that list
@@ -211,50 +212,61 @@ pg_status check_var(const pg_composer *c, pg_variable v) {
     return PG_OK;
 }
 
-// one pass over n words of a device array on the composer's stream: their maximum into out[0], their salted digest into out[1], out[2]
-void digest_words(pg_composer *c, const uint64_t *d, uint64_t n, unsigned long long *d_out, unsigned long long salt) {
-    const uint64_t want = (n + pg::kThreads - 1) / pg::kThreads, most = (uint64_t)c->e->num_cus * 8;
-    hipLaunchKernelGGL(pg::max_variable_kernel, dim3((uint32_t)(want < most ? want : most)), dim3(pg::kThreads), 0, c->stream, d, n, d_out, salt);
+// The preflight of an append on device arrays, in ONE host synchronisation.  The composer's result block (digest.hpp) is cleared on
+// its stream -- zeros, but the first `firsts` words of `call` ~0: the call's first offenders --, enqueue(block) launches the call's
+// passes over its arrays, and the block comes back as r.  Every entry of the Variable arrays must be a Variable of this composer
+// (the reference panics on an unknown one): that comes before the call's own preconditions, which the caller reads from r.call.
+// Nothing has been appended when it fails.
+template <class Enqueue>
+pg_status preflight(pg_composer *c, unsigned firsts, pg::Preflight &r, Enqueue enqueue) {
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    pg::Preflight *d = c->d_preflight.as<pg::Preflight>();
+    PG_HIP_TRY(hipMemsetAsync(d, 0, sizeof *d, c->stream));
+    if (firsts) PG_HIP_TRY(hipMemsetAsync(d->call, 0xff, firsts * sizeof d->call[0], c->stream));
+    enqueue(d);
+    PG_HIP_TRY(hipGetLastError());
+    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d, sizeof *d, hipMemcpyDeviceToHost, c->stream));
+    PG_HIP_TRY(hipStreamSynchronize(c->stream));
+    r = *c->h_total.as<pg::Preflight>();
+    if (r.max_var < c->nvars) return PG_OK;
+    return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(r.max_var) + " in a batched append (the composer has " +
+                                             std::to_string(c->nvars) + ")");
 }
-// device arrays of Variables handed to a batched append: every entry must be a Variable of this composer.  One small
-// reduction per array on the composer's stream and one host synchronisation; nothing has been appended when it fails.
-// The same pass digests the arrays (128 bits over values and positions, the arrays salted by their place in the list):
-// what an append's rows depend on when its wires come from device memory (`digest`, for its signature).
+pg_composer::Sig sig_of(const pg::Digest &d) { return pg_composer::Sig{d.h1, d.h2}; }
+// a preflight's pass over n words of a device array: their maximum into *max, and into *dg what they add to a digest under `salt`
+void digest_words(pg_composer *c, const void *a, uint64_t n, unsigned long long *max, pg::Digest *dg, unsigned long long salt) {
+    hipLaunchKernelGGL(pg::max_variable_kernel, dim3(grid_cap((n + pg::kThreads - 1) / pg::kThreads, (uint64_t)c->e->num_cus * 8)),
+                       dim3(pg::kThreads), 0, c->stream, static_cast<const uint64_t *>(a), n, max, dg, salt);
+}
+// ... over the call's place-th array of Variables (NULL: the place is kept, nothing is read)
+void digest_vars(pg_composer *c, const pg_variable *a, uint64_t n, pg::Preflight *d, unsigned place) {
+    if (a) digest_words(c, a, n, &d->max_var, &d->vars, pg::var_array_salt(place));
+}
+// device arrays of Variables handed to a batched append: the preflight of the calls with no other device array.  `digest`: 128 bits
+// over values and positions, the arrays salted by their place in the list -- what an append's rows depend on when its wires come
+// from device memory (for its signature).
 pg_status check_var_arrays(pg_composer *c, std::initializer_list<const pg_variable *> arrays, uint64_t batch,
                            pg_composer::Sig *digest = nullptr) {
     if (digest) *digest = pg_composer::Sig{0, 0};
     if (batch == 0) return PG_OK;
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);  // the staging blob's last three words
-    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
-    unsigned long long salt = 0x243f6a8885a308d3ull;
-    for (const pg_variable *a : arrays) {
-        salt += 0x9e3779b97f4a7c15ull;
-        if (a) digest_words(c, a, batch, d_out, salt);
-    }
-    PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
-    PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    if (c->totals()[0] >= c->nvars)
-        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(c->totals()[0]) + " in a batched append (the composer has " +
-                                                 std::to_string(c->nvars) + ")");
-    if (digest) *digest = pg_composer::Sig{c->totals()[1], c->totals()[2]};
+    pg::Preflight r;
+    PG_TRY(preflight(c, 0, r, [&](pg::Preflight *d) {
+        unsigned place = 0;
+        for (const pg_variable *a : arrays) digest_vars(c, a, batch, d, place++);
+    }));
+    if (digest) *digest = sig_of(r.vars);
     return PG_OK;
 }
-// the same digest of a device array of scalars (per-item public bounds): n * 4 words; d2 (may be NULL): a second such array, salted
-// by its place like check_var_arrays' (the two arrays swapped digest differently)
-pg_status digest_scalars(pg_composer *c, const pg_scalar *d, uint64_t n, pg_composer::Sig *digest, const pg_scalar *d2 = nullptr) {
-    *digest = pg_composer::Sig{0, 0};
-    if (n == 0) return PG_OK;
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 37);
-    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 24, c->stream));
-    digest_words(c, reinterpret_cast<const uint64_t *>(d), 4 * n, d_out, 0x13198a2e03707344ull);
-    if (d2) digest_words(c, reinterpret_cast<const uint64_t *>(d2), 4 * n, d_out, 0x13198a2e03707344ull + 0x9e3779b97f4a7c15ull);
-    PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 24, hipMemcpyDeviceToHost, c->stream));
-    PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    *digest = pg_composer::Sig{c->totals()[1], c->totals()[2]};
+// the preflight of the ragged ladders: the digest of their device arrays of per-item public bounds, n > 0 scalars each (the caller has
+// returned on an empty batch; d2 may be NULL; the two arrays swapped digest differently).  No Variable comes from outside: max_var
+// stays 0, which every composer knows (zero_var), and the words' maximum goes to call[0], which these calls do not read.
+pg_status bounds_digest(pg_composer *c, const pg_scalar *d1, const pg_scalar *d2, uint64_t n, pg_composer::Sig *digest) {
+    pg::Preflight r;
+    PG_TRY(preflight(c, 0, r, [&](pg::Preflight *d) {
+        digest_words(c, d1, 4 * n, &d->call[0], &d->others, pg::scalar_array_salt(0));
+        if (d2) digest_words(c, d2, 4 * n, &d->call[0], &d->others, pg::scalar_array_salt(1));
+    }));
+    *digest = sig_of(r.others);
     return PG_OK;
 }
 
@@ -602,9 +614,10 @@ pg_status pg_composer_create(pg_engine *e, uint64_t gate_capacity, uint64_t var_
     if (!c) return fail(PG_ERR_HIP, "out of host memory");
     c->e = e;
     c->stream = static_cast<hipStream_t>(stream);
-    if (c->cols.create(gate_capacity, var_capacity) != PG_OK || c->d_stage.reserve(sizeof(pg::StageBlob)) != PG_OK)
+    if (c->cols.create(gate_capacity, var_capacity) != PG_OK || c->d_stage.reserve(sizeof(pg::StageBlob)) != PG_OK ||
+        c->d_preflight.reserve(sizeof(pg::Preflight)) != PG_OK)
         return fail(PG_ERR_HIP, "hipMalloc of the composer columns failed");
-    PG_TRY(c->h_total.reserve(64));
+    PG_TRY(c->h_total.reserve(sizeof(pg::Preflight)));
     // StandardComposer::new(): zero_var = add_witness_to_circuit_description(0), then add_dummy_constraints()
     pg_scalar zero, s;
     from_fr(pg::fr_zero(), &zero);
@@ -1195,34 +1208,24 @@ pg_status interval_bounds(const pg_scalar *min, const pg_scalar *max, uint64_t n
         return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: max - min does not fit num_bits = " + std::to_string(num_bits) + " bits");
     return PG_OK;
 }
-// The device arrays of the per-item form in ONE host synchronisation (the one check_var_arrays pays): the Variables' maximum and
-// digest, and, from ONE pass over the two bound arrays (interval_bounds_kernel), their digest and the items whose bounds violate the
-// preconditions.
+// The preflight of the per-item form: the Variables' pass and ONE pass over the two bound arrays (interval_bounds_kernel), which
+// leaves their digest and the items whose bounds violate the preconditions.
 pg_status check_interval_arrays(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *d_min, const pg_scalar *d_max,
                                 uint64_t num_bits, uint64_t batch, pg_composer::Sig *vars_dg, pg_composer::Sig *bounds_dg) {
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    // the staging blob's last eight words: [bad items, first bad item, the bounds' digest | (unused) | check_var_arrays' three]
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 32);
-    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 64, c->stream));
-    PG_HIP_TRY(hipMemsetAsync(d_out + 1, 0xff, 8, c->stream));
-    digest_words(c, d_witness_var, batch, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
-    // (its waves end in contended atomics: interval_gate.hpp)
-    const uint64_t want = (batch + pg::kThreads - 1) / pg::kThreads, few = (uint64_t)c->e->num_cus * 2;
-    hipLaunchKernelGGL(pg::interval_bounds_kernel, dim3((uint32_t)(want < few ? want : few)), dim3(pg::kThreads), 0, c->stream,
-                       reinterpret_cast<const uint4 *>(d_min), reinterpret_cast<const uint4 *>(d_max), batch, (uint32_t)num_bits, d_out);
-    PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 64, hipMemcpyDeviceToHost, c->stream));
-    PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t *t = c->totals();
-    if (t[5] >= c->nvars)
-        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(t[5]) + " in a batched append (the composer has " +
-                                                 std::to_string(c->nvars) + ")");
-    if (t[0])
-        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: the bounds of " + std::to_string(t[0]) + " items are not reduced, have min > max or "
-                                             "max - min beyond num_bits = " + std::to_string(num_bits) + " bits; the first is item " +
-                                                 std::to_string(t[1]));
-    *vars_dg = pg_composer::Sig{t[6], t[7]};
-    *bounds_dg = pg_composer::Sig{t[2], t[3]};
+    pg::Preflight r;
+    PG_TRY(preflight(c, 1, r, [&](pg::Preflight *d) {
+        digest_vars(c, d_witness_var, batch, d, 0);
+        // (its waves end in contended atomics: interval_gate.hpp)
+        hipLaunchKernelGGL(pg::interval_bounds_kernel, dim3(grid_cap((batch + pg::kThreads - 1) / pg::kThreads, (uint64_t)c->e->num_cus * 2)),
+                           dim3(pg::kThreads), 0, c->stream, reinterpret_cast<const uint4 *>(d_min), reinterpret_cast<const uint4 *>(d_max),
+                           batch, (uint32_t)num_bits, d);
+    }));
+    if (r.call[pg::kIntervalBadItems])
+        return fail(PG_ERR_INVALID_ARGUMENT, "interval_gate: the bounds of " + std::to_string(r.call[pg::kIntervalBadItems]) +
+                                                 " items are not reduced, have min > max or max - min beyond num_bits = " +
+                                                 std::to_string(num_bits) + " bits; the first is item " + std::to_string(r.call[pg::kIntervalFirstBad]));
+    *vars_dg = sig_of(r.vars);
+    *bounds_dg = sig_of(r.others);
     return PG_OK;
 }
 
@@ -1301,38 +1304,27 @@ pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t n
 }  // extern "C"
 
 namespace {
-// The device arrays of a weighted sum in ONE host synchronisation (the one check_var_arrays pays): the terms' maximum and digest, and,
-// from one pass over seg_off, the coefficients and the constants (weighted_sum_check_kernel), their digest and the first entry of
-// each that violates a precondition.  Nothing has used an entry of seg_off as an index before this returns PG_OK.
+// The preflight of a weighted sum: the terms' pass and one pass over seg_off, the coefficients and the constants
+// (weighted_sum_check_kernel), which leaves their digest and the first entry of each that violates a precondition.  Nothing has used
+// an entry of seg_off as an index before this returns PG_OK.
 pg_status check_weighted_sum_arrays(pg_composer *c, const pg_variable *d_term_var, const uint64_t *d_seg_off, const pg_scalar *d_coeff,
                                     const pg_scalar *d_constant, uint64_t terms, uint64_t segments, pg_composer::Sig *vars_dg,
                                     pg_composer::Sig *arrays_dg) {
-    PG_HIP_TRY(hipSetDevice(c->e->device));
-    // the staging blob's last eight words: [first bad segment, coefficient, constant | the three arrays' digest | check_var_arrays' three]
-    unsigned long long *d_out = reinterpret_cast<unsigned long long *>(c->stage_words() + 32);
-    PG_HIP_TRY(hipMemsetAsync(d_out, 0, 64, c->stream));
-    PG_HIP_TRY(hipMemsetAsync(d_out, 0xff, 24, c->stream));
-    digest_words(c, d_term_var, terms, d_out + 5, 0x243f6a8885a308d3ull + 0x9e3779b97f4a7c15ull);
-    const uint64_t want = (terms + pg::kThreads - 1) / pg::kThreads, few = (uint64_t)c->e->num_cus * 2;
-    hipLaunchKernelGGL(pg::weighted_sum_check_kernel, dim3((uint32_t)(want < few ? want : few)), dim3(pg::kThreads), 0, c->stream, d_seg_off,
-                       reinterpret_cast<const uint4 *>(d_coeff), reinterpret_cast<const uint4 *>(d_constant), terms, segments, d_out);
-    PG_HIP_TRY(hipGetLastError());
-    PG_HIP_TRY(hipMemcpyAsync(c->totals(), d_out, 64, hipMemcpyDeviceToHost, c->stream));
-    PG_HIP_TRY(hipStreamSynchronize(c->stream));
-    const uint64_t *t = c->totals();
-    if (t[5] >= c->nvars)
-        return fail(PG_ERR_INVALID_ARGUMENT, "unknown Variable " + std::to_string(t[5]) + " in a batched append (the composer has " +
-                                                 std::to_string(c->nvars) + ")");
-    if (t[0] != ~0ull)
+    pg::Preflight r;
+    PG_TRY(preflight(c, 3, r, [&](pg::Preflight *d) {
+        digest_vars(c, d_term_var, terms, d, 0);
+        hipLaunchKernelGGL(pg::weighted_sum_check_kernel, dim3(grid_cap((terms + pg::kThreads - 1) / pg::kThreads, (uint64_t)c->e->num_cus * 2)),
+                           dim3(pg::kThreads), 0, c->stream, d_seg_off, reinterpret_cast<const uint4 *>(d_coeff),
+                           reinterpret_cast<const uint4 *>(d_constant), terms, segments, d);
+    }));
+    const unsigned long long seg = r.call[pg::kWsBadSegment], co = r.call[pg::kWsBadCoeff], k = r.call[pg::kWsBadConstant];
+    if (seg != ~0ull)
         return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: d_seg_off must start at 0, end at terms = " + std::to_string(terms) +
-                                                 " and give every segment at least 2 terms; the first offending segment is " +
-                                                 std::to_string(t[0]));
-    if (t[1] != ~0ull)
-        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: coefficient " + std::to_string(t[1]) + " is not reduced below the modulus");
-    if (t[2] != ~0ull)
-        return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: constant " + std::to_string(t[2]) + " is not reduced below the modulus");
-    *vars_dg = pg_composer::Sig{t[6], t[7]};
-    *arrays_dg = pg_composer::Sig{t[3], t[4]};
+                                                 " and give every segment at least 2 terms; the first offending segment is " + std::to_string(seg));
+    if (co != ~0ull) return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: coefficient " + std::to_string(co) + " is not reduced below the modulus");
+    if (k != ~0ull) return fail(PG_ERR_INVALID_ARGUMENT, "weighted_sum: constant " + std::to_string(k) + " is not reduced below the modulus");
+    *vars_dg = sig_of(r.vars);
+    *arrays_dg = sig_of(r.others);
     return PG_OK;
 }
 
@@ -1515,7 +1507,7 @@ static pg_status ragged_ladder_batch(pg_composer *c, uint32_t wire_kind, SigKind
         },
         [&](uint64_t, pg_composer::Sig *sig) {
             pg_composer::Sig dg;
-            PG_TRY(digest_scalars(c, d_max_range, batch, &dg, with_min ? d_min_range : nullptr));
+            PG_TRY(bounds_digest(c, d_max_range, with_min ? d_min_range : nullptr, batch, &dg));
             *sig = gadget_sig(c, kind, pg::fr_zero(), pg::fr_zero(), batch, 0, dg);
             return PG_OK;
         },

@@ -6,6 +6,7 @@
 #pragma once
 
 #include "composer_cols.hpp"
+#include "digest.hpp"
 #include "emit.hpp"
 
 namespace pg {
@@ -165,41 +166,31 @@ __global__ __launch_bounds__(kThreads) void gate_batch_kernel(const GateBatch B_
     }
 }
 
-// largest entry of a device array of Variables -> out[0] (atomicMax; starts at 0): the batched appends check it against the
-// composer's variable count before anything is appended (the reference panics on an unknown Variable).  In the same pass a
-// 128-bit digest of the array -> out[1], out[2] (sums of two position-salted 64-bit mixes: order of summation does not matter,
-// order of the entries does): an append whose rows depend on the array is signed with it (pg_composer_clear_witness).
-__device__ __forceinline__ unsigned long long digest_mix(unsigned long long x) {
-    x ^= x >> 30; x *= 0xbf58476d1ce4e5b9ull;
-    x ^= x >> 27; x *= 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
-__global__ __launch_bounds__(kThreads) void max_variable_kernel(const uint64_t *a, uint64_t n, unsigned long long *out,
+// largest entry of a device array of Variables -> *max (atomicMax; starts at 0): the batched appends check it against the
+// composer's variable count before anything is appended (the reference panics on an unknown Variable).  In the same pass the
+// array's words, salted, are added to *dg (digest.hpp): an append whose rows depend on the array is signed with it
+// (pg_composer_clear_witness).
+__global__ __launch_bounds__(kThreads) void max_variable_kernel(const uint64_t *a, uint64_t n, unsigned long long *max, Digest *dg,
                                                                unsigned long long salt) {
-    unsigned long long m = 0, h1 = 0, h2 = 0;
+    unsigned long long m = 0;
+    Digest h{0, 0};
     for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < n; i += (uint64_t)gridDim.x * kThreads) {
         const unsigned long long v = a[i];
         m = v > m ? v : m;
-        h1 += digest_mix(v + digest_mix(i + salt));
-        h2 += digest_mix((v ^ 0x9e3779b97f4a7c15ull) * 0xff51afd7ed558ccdull + i * 0xc4ceb9fe1a85ec53ull + salt);
+        h.add(v, i, salt);
     }
 #pragma unroll
     for (int d = 32; d >= 1; d >>= 1) {
         const unsigned long long o = __shfl_xor(m, d, 64);
         m = o > m ? o : m;
-        h1 += __shfl_xor(h1, d, 64);
-        h2 += __shfl_xor(h2, d, 64);
     }
-    if ((threadIdx.x & 63) == 0) {
-        if (m) atomicMax(out, m);
-        atomicAdd(out + 1, h1);
-        atomicAdd(out + 2, h2);
-    }
+    if ((threadIdx.x & 63) == 0 && m) atomicMax(max, m);
+    digest_flush(h, dg);
 }
 
 // small host blob -> device staging buffer (inputs of single-gadget calls: scalars, Variables, offsets)
 struct StageBlob {
-    uint64_t w[40];
+    uint64_t w[8];
 };
 __global__ void stage_kernel(const StageBlob blob, uint64_t *dst, uint32_t n) {
     if (threadIdx.x < n) dst[threadIdx.x] = blob.w[threadIdx.x];

@@ -64,6 +64,17 @@ PG_HD uint64_t mac64(uint64_t a, uint64_t b, uint64_t c, uint64_t &carry) {
     return (uint64_t)t;
 }
 
+// x < y as 256-bit integers, on raw limbs, from the top (compares, no borrow chain: a kernel that holds both keeps fewer registers)
+PG_HD bool raw_less(const Fr &x, const Fr &y) {
+    bool less = false, open = true;
+    for (int k = 3; k >= 0; k--) {
+        if (open && x.l[k] != y.l[k]) { less = x.l[k] < y.l[k]; open = false; }
+    }
+    return less;
+}
+// raw limbs below the modulus
+PG_HD bool fr_raw_is_reduced(const Fr &a) { return raw_less(a, fr_modulus()); }
+
 // r (with a virtual 5th limb `top`, value < 2q) -> r mod q
 PG_HD Fr fr_final_sub(const uint64_t r[4], uint64_t top) {
     uint64_t bw = 0;

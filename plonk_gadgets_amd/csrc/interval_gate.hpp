@@ -107,15 +107,16 @@ struct IntervalGateGD {
 };
 
 // per-item bounds against the preconditions, as canonical integers: both below r, lo <= hi, hi - lo < 2^num_bits.  One lane per
-// item at a time; out[0] += the items that violate one, out[1] = min of the first such item (starts at ~0).  The lane has the item's eight
-// words in registers, so the same pass digests the two arrays for the call's signature (out[2], out[3] += position-salted mixes
-// as max_variable_kernel's: a bound moved, or two items' bounds swapped, is another call to pg_composer_clear_witness).  Every wave
-// ends in two atomics on the same two words, which the memory system serialises (about 12 ns each on MI355X): the grid is a few
-// workgroups per CU that stride over the items, not one workgroup per 256 items -- 16 384 waves' atomics took 405 us at 2^20 items
-// where the arrays' 64 MiB are read in 40
+// item at a time; out->call[kIntervalBadItems] += the items that violate one, out->call[kIntervalFirstBad] = min of the first such item
+// (it starts at ~0).  The lane has the item's eight words in registers, so the same pass digests the two arrays for the call's
+// signature (out->others, digest.hpp: the pairs as ONE array of eight words per item -- a bound moved, the two arrays swapped, or two
+// items' bounds swapped, is another call to pg_composer_clear_witness).  Every wave ends in two atomics on the same two words, which
+// the memory system serialises (about 12 ns each on MI355X): the grid is a few workgroups per CU that stride over the items, not one
+// workgroup per 256 items -- 16 384 waves' atomics took 405 us at 2^20 items where the arrays' 64 MiB are read in 40
+enum : int { kIntervalFirstBad = 0, kIntervalBadItems = 1 };  // Preflight::call
 __global__ __launch_bounds__(kThreads) void interval_bounds_kernel(const uint4 *min_v, const uint4 *max_v, uint64_t batch, uint32_t num_bits,
-                                                                   unsigned long long *out) {
-    unsigned long long h1 = 0, h2 = 0;
+                                                                   Preflight *out) {
+    Digest h{0, 0};
     for (uint64_t i = (uint64_t)blockIdx.x * kThreads + threadIdx.x; i < batch; i += (uint64_t)gridDim.x * kThreads) {
         FrVec lo, hi;
         lo.v[0] = min_v[2 * i];
@@ -123,39 +124,17 @@ __global__ __launch_bounds__(kThreads) void interval_bounds_kernel(const uint4 *
         hi.v[0] = max_v[2 * i];
         hi.v[1] = max_v[2 * i + 1];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            const unsigned long long w = j < 4 ? lo.f.l[j] : hi.f.l[j - 4], at = 8 * i + j;
-            h1 += digest_mix(w + digest_mix(at + 0x13198a2e03707344ull));
-            h2 += digest_mix((w ^ 0x9e3779b97f4a7c15ull) * 0xff51afd7ed558ccdull + at * 0xc4ceb9fe1a85ec53ull);
-        }
-        const Fr q = fr_modulus();
-        // x >= y on raw limbs, from the top
-        auto ge = [](const Fr &x, const Fr &y) {
-            bool r = true, open = true;
-#pragma unroll
-            for (int k = 3; k >= 0; k--) {
-                if (open && x.l[k] != y.l[k]) { r = x.l[k] > y.l[k]; open = false; }
-            }
-            return r;
-        };
-        bool bad = ge(lo.f, q) || ge(hi.f, q) || !ge(fr_from_mont(hi.f), fr_from_mont(lo.f));
+        for (int j = 0; j < 8; j++) h.add(j < 4 ? lo.f.l[j] : hi.f.l[j - 4], 8 * i + j, scalar_array_salt(0));
+        bool bad = !fr_raw_is_reduced(lo.f) || !fr_raw_is_reduced(hi.f) || raw_less(fr_from_mont(hi.f), fr_from_mont(lo.f));
         // hi >= lo: the field difference is the integer one
         const Fr top = raw_shr(fr_from_mont(fr_sub(hi.f, lo.f)), num_bits);
         bad = bad || (top.l[0] | top.l[1] | top.l[2] | top.l[3]) != 0;
         if (bad) {
-            atomicAdd(out, 1ull);
-            atomicMin(out + 1, (unsigned long long)i);
+            atomicAdd(&out->call[kIntervalBadItems], 1ull);
+            atomicMin(&out->call[kIntervalFirstBad], (unsigned long long)i);
         }
     }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        h1 += __shfl_xor(h1, d, 64);
-        h2 += __shfl_xor(h2, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(out + 2, h1);
-        atomicAdd(out + 3, h2);
-    }
+    digest_flush(h, &out->others);
 }
 
 }  // namespace pg

@@ -192,16 +192,6 @@ PG_HD uint64_t sides_load_u64(const uint8_t *p) {
 #endif
 }
 
-// raw limbs below the modulus
-PG_HD bool fr_raw_is_reduced(const Fr &a) {
-    uint64_t bw = 0;
-    (void)sbb64(a.l[0], PG_Q0, bw);
-    (void)sbb64(a.l[1], PG_Q1, bw);
-    (void)sbb64(a.l[2], PG_Q2, bw);
-    (void)sbb64(a.l[3], PG_Q3, bw);
-    return bw != 0;
-}
-
 PG_HD Fr sides_raw_eval(const uint8_t *proof, uint32_t k) {
     const uint8_t *p = proof + kSidesEvalOffset + 32 * k;
     return Fr{{sides_load_u64(p), sides_load_u64(p + 8), sides_load_u64(p + 16), sides_load_u64(p + 24)}};

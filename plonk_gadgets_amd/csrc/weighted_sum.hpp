@@ -287,60 +287,40 @@ __global__ __launch_bounds__(kThreads) void weighted_sum_write_kernel(const Weig
 }
 
 // The call's other device arrays against its preconditions, and their digest, in one launch:
-//   seg_off[0] == 0, seg_off[segments] == terms, every segment >= 2 terms     first offender -> out[0] (atomicMin; starts at ~0)
-//   every coefficient (coeff != NULL) below r                                 -> out[1]
-//   every constant (konst != NULL) below r                                    -> out[2]
-//   out[3], out[4] += position-salted mixes of every word of the three arrays (max_variable_kernel's; each array salted apart)
+//   seg_off[0] == 0, seg_off[segments] == terms, every segment >= 2 terms     first offender -> out->call[kWsBadSegment]
+//   every coefficient (coeff != NULL) below r                                 -> out->call[kWsBadCoeff]
+//   every constant (konst != NULL) below r                                    -> out->call[kWsBadConstant]
+//   (atomicMin; each starts at ~0)
+//   out->others += every word of the three arrays, each array under its own salt (digest.hpp)
 // A grid of a few workgroups per CU that stride over the entries: every wave ends in two atomics on the same words
 // (interval_gate.hpp says what 16 384 waves' cost).
-__device__ __forceinline__ bool ws_reduced(const Fr &x) {
-    const Fr q = fr_modulus();
-    bool below = false, open = true;
-#pragma unroll
-    for (int k = 3; k >= 0; k--) {
-        if (open && x.l[k] != q.l[k]) { below = x.l[k] < q.l[k]; open = false; }
-    }
-    return below;
-}
-__device__ __forceinline__ void ws_digest(unsigned long long w, unsigned long long at, unsigned long long salt, unsigned long long &h1,
-                                          unsigned long long &h2) {
-    h1 += digest_mix(w + digest_mix(at + salt));
-    h2 += digest_mix((w ^ 0x9e3779b97f4a7c15ull) * 0xff51afd7ed558ccdull + at * 0xc4ceb9fe1a85ec53ull + salt);
-}
+enum : int { kWsBadSegment = 0, kWsBadCoeff = 1, kWsBadConstant = 2 };  // Preflight::call
 __global__ __launch_bounds__(kThreads) void weighted_sum_check_kernel(const uint64_t *seg_off, const uint4 *coeff, const uint4 *konst,
-                                                                      uint64_t terms, uint64_t segments, unsigned long long *out) {
-    unsigned long long h1 = 0, h2 = 0;
+                                                                      uint64_t terms, uint64_t segments, Preflight *out) {
+    Digest h{0, 0};
     const uint64_t lane = (uint64_t)blockIdx.x * kThreads + threadIdx.x, stride = (uint64_t)gridDim.x * kThreads;
     for (uint64_t s = lane; s < segments; s += stride) {
         const uint64_t a = seg_off[s], b = seg_off[s + 1];
-        if (s == 0) ws_digest(a, 0, 0x452821e638d01377ull, h1, h2);
-        ws_digest(b, s + 1, 0x452821e638d01377ull, h1, h2);
+        if (s == 0) h.add(a, 0, kSaltSegOff);
+        h.add(b, s + 1, kSaltSegOff);
         const bool bad = (s == 0 && a != 0) || b < a || b - a < 2 || (s == segments - 1 && b != terms);
-        if (bad) atomicMin(out, (unsigned long long)s);
+        if (bad) atomicMin(&out->call[kWsBadSegment], (unsigned long long)s);
     }
     if (coeff)
         for (uint64_t t = lane; t < terms; t += stride) {
             const Fr x = ws_load(coeff, t);
 #pragma unroll
-            for (int j = 0; j < 4; j++) ws_digest(x.l[j], 4 * t + j, 0xbe5466cf34e90c6cull, h1, h2);
-            if (!ws_reduced(x)) atomicMin(out + 1, (unsigned long long)t);
+            for (int j = 0; j < 4; j++) h.add(x.l[j], 4 * t + j, kSaltCoeff);
+            if (!fr_raw_is_reduced(x)) atomicMin(&out->call[kWsBadCoeff], (unsigned long long)t);
         }
     if (konst)
         for (uint64_t s = lane; s < segments; s += stride) {
             const Fr x = ws_load(konst, s);
 #pragma unroll
-            for (int j = 0; j < 4; j++) ws_digest(x.l[j], 4 * s + j, 0xc0ac29b7c97c50ddull, h1, h2);
-            if (!ws_reduced(x)) atomicMin(out + 2, (unsigned long long)s);
+            for (int j = 0; j < 4; j++) h.add(x.l[j], 4 * s + j, kSaltConstant);
+            if (!fr_raw_is_reduced(x)) atomicMin(&out->call[kWsBadConstant], (unsigned long long)s);
         }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-        h1 += __shfl_xor(h1, d, 64);
-        h2 += __shfl_xor(h2, d, 64);
-    }
-    if ((threadIdx.x & 63) == 0) {
-        atomicAdd(out + 3, h1);
-        atomicAdd(out + 4, h2);
-    }
+    digest_flush(h, &out->others);
 }
 
 }  // namespace pg

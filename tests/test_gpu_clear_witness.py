@@ -617,6 +617,16 @@ def a_add_b(dev, ora, first, seed):
         same_vars(r, [ora.L.composer_add(ora.c, F(3), x, F(Q - 1), y, F(9), None) for x, y in zip(a, b)])
 
 
+def a_wsum(dev, ora, first, seed):
+    """three segments of two terms: as many rows as add_batch's, at the same place"""
+    from tests import weighted_sum_oracle as wso
+    x, off = [first, first + 1, first + 2, first + 3, first + 4, first + 1], [0, 2, 4, 6]
+    co, ks = [3, Q - 1, 1, 0, 5, 2], [9, 0, Q - 1]
+    r = dev.weighted_sum_ragged_batch(tv(x), tv(off), t(synth.scalars_from_ints(co)), t(synth.scalars_from_ints(ks)))
+    if ora is not None:
+        same_vars(r, wso.replay(ora, x, off, co, ks))
+
+
 def a_mul_b(dev, ora, first, seed):
     a, b = [first, first + 1, first + 2], [first + 3, first + 4, first]
     r = dev.mul_batch(S(3), tv(a), tv(b), S(9))
@@ -691,7 +701,7 @@ SIGNED_APPENDS = [
     ("scalar_decomposition_batch", a_dec), ("is_non_zero_batch", a_inz), ("scalar_mix_batch", a_mix),
     ("conditionally_select_zero_batch", two_input("conditionally_select_zero")),
     ("conditionally_select_one_batch", two_input("conditionally_select_one")), ("maybe_equal_batch", two_input("maybe_equal")),
-    ("add_batch", a_add_b), ("mul_batch", a_mul_b), ("poly_gate_batch", a_poly_b),
+    ("add_batch", a_add_b), ("weighted_sum_ragged_batch", a_wsum), ("mul_batch", a_mul_b), ("poly_gate_batch", a_poly_b),
     ("constrain_to_constant_batch", a_ctc_b), ("boolean_gate_batch", a_bool_b),
 ]
 
