@@ -7,7 +7,8 @@ The reference's loop
     for w in witnesses { let a = AllocatedScalar::allocate(composer, w); results.push(range_check(composer, min, max, a)); }
 is one batched append on the device-resident composer; single calls with the reference's signatures mix in freely.  Then a
 per-account limit check: every amount in 16 bits, limit - (the account's amounts) by ONE weighted_sum_ragged_batch over ragged
-accounts, and the headrooms in 16 bits again.
+accounts, and the headrooms in 16 bits again.  Last, a small circuit of its own that is proven and verified: min(x, y) of pairs of
+64-bit amounts, from the bit [x <= y] (is_less_equal_each) and gate batches.
 """
 import os
 import sys
@@ -76,6 +77,41 @@ def main():
     print("%d witnesses and the limit check -> %d rows, %d variables: the witnesses' rows built in %.2f ms (%.3g constraints/s), prover-ready in another %.2f ms"
           % (batch, n, composer.num_variables(), t_build * 1e3, built_rows / t_build, t_ready * 1e3))
     assert full["q_arith"].shape == (n, 4) and sigma.shape == (4, padded)
+    min_of_two(engine)
+
+
+def min_of_two(engine, pairs=8):
+    """min(x, y) = y + [x <= y] (x - y) of two 64-bit amounts; proven, then verified"""
+    S = pg.BlsScalar.from_int
+    rnd = np.random.default_rng(7)
+    xs = [int(v) for v in rnd.integers(0, 1 << 63, pairs)]
+    ys = [int(v) for v in rnd.integers(0, 1 << 63, pairs)]
+    ys[0], xs[1] = xs[0], 2**64 - 1                                              # a tie, and the largest amount
+    composer = pg.StandardComposer(engine)
+    composer.auto_grow()
+    first = composer.add_input_batch(torch.from_numpy(synth.scalars_from_ints(xs + ys).view(np.int64)).to("cuda:0"))
+    x = torch.arange(first, first + pairs, dtype=torch.int64, device="cuda:0")
+    y = x + pairs
+    composer.range_gate_batch(x, 64)                                             # the comparison's precondition: both below 2^64
+    composer.range_gate_batch(y, 64)
+    bit = composer.is_less_equal_each(x, y, 64)                                  # [x <= y], 12 rows an item
+    diff = composer.add_batch(S(1), x, S(synth.Q - 1), y, S(0))                  # x - y (in the field)
+    part = composer.conditionally_select_zero_batch(diff, bit)                   # x - y where x <= y, else 0
+    smaller = composer.add_batch(S(1), y, S(1), part, S(0))
+    composer.sync()
+    assert composer.check() == -1
+    values = np.ascontiguousarray(np.asarray(composer.export()["var_values"])).view(np.uint64).reshape(-1, 4)
+    assert [synth.to_int(values[v]) for v in smaller.cpu().tolist()] == [min(a, b) for a, b in zip(xs, ys)]
+    n = 1 << (composer.circuit_size() - 1).bit_length()
+    tau = S(0x5EED_7A0 ** 9)
+    ck, ok = pg.CommitKey.setup(engine, n + 7, tau), pg.OpeningKey.setup(engine, tau)
+    pre = composer.preprocessed_commitments(ck)
+    proof = composer.prove(ck, b"plonk", pre, blinding=True)
+    assert proof.verify(pg.VerifierKey(n, pre), ok, {})
+    print("min(x, y) of %d pairs of 64-bit amounts: %d rows, proven (blinded, %d bytes) and verified"
+          % (pairs, composer.circuit_size(), len(proof.to_bytes())))
+    ok.close()
+    composer.close()
 
 
 if __name__ == "__main__":

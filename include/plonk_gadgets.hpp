@@ -275,6 +275,12 @@ inline void interval_gate(StandardComposer &c, const pg_variable *d_witness_var,
                           uint64_t batch) {
     pg_throw(pg_composer_interval_gate_ragged_batch(c.h, d_witness_var, d_min, d_max, num_bits, batch), "Batched::interval_gate (ragged)");
 }
+// d_result_vars[i] = the Variable that holds [x_i <= y_i] ([x_i < y_i] when strict), PROVIDED the circuit bounds both below 2^num_bits
+// (num_bits even, 2..252): one such widget over num_bits + 2 bits on 2^num_bits + y - x - strict, ceil((num_bits / 2 + 1) / 3) + 1 rows
+inline void is_less_equal(StandardComposer &c, const pg_variable *d_x_var, const pg_variable *d_y_var, uint64_t num_bits, bool strict,
+                          uint64_t batch, pg_variable *d_result_vars) {
+    pg_throw(pg_composer_is_less_equal_batch(c.h, d_x_var, d_y_var, num_bits, strict ? 1 : 0, batch, d_result_vars), "Batched::is_less_equal");
+}
 // result[s] = d_constant[s] + sum over t in d_seg_off[s] .. d_seg_off[s + 1] - 1 of d_coeff[t] * d_term_var[t], as the chain of composer.add calls
 // (every segment >= 2 terms; d_coeff / d_constant / d_result_vars may be NULL: all 1 / all 0 / not wanted): terms - segments rows
 inline void weighted_sum(StandardComposer &c, const pg_variable *d_term_var, const uint64_t *d_seg_off, const pg_scalar *d_coeff,

@@ -487,6 +487,25 @@ pg_status pg_composer_interval_gate_batch(pg_composer *c, const pg_variable *d_w
 pg_status pg_composer_interval_gate_ragged_batch(pg_composer *c, const pg_variable *d_witness_var, const pg_scalar *d_min,
                                                  const pg_scalar *d_max, uint64_t num_bits, uint64_t batch);
 
+/* is_less_equal(x, y, num_bits, strict): the bit [x <= y] ([x < y] when strict != 0) of two WITNESSES as a Variable the rest of the
+ * circuit can use, from ONE range widget (above) over num_bits + 2 bits on z = 2^num_bits + y - x - s, s = 1 if strict else 0;
+ * DESIGN 3.23.  num_bits even, 2 <= num_bits <= 252 (2^(num_bits + 1) < r), else PG_ERR_INVALID_ARGUMENT with nothing appended and
+ * the results untouched.  With K = num_bits + 2, k = K / 2, g = ceil(k / 3), pad = 3g - k and c(z) the canonical integer of z an item
+ * owns g + 1 rows and k new Variables:
+ *   first + kk = c(z) >> 2 (k - 1 - kk), kk = 0 .. k - 1: `first` is the top quad of c(z) -- the RESULT --, first + k - 1 is z
+ *   P(p) = zero_var (p <= pad);  first + (p - pad - 1) (pad < p <= 3g, so P(3g) = z)
+ *   row i < g = (P(3i), P(3i+1), P(3i+2)), q_range = 1, all five arithmetic selectors 0
+ *   row g = (z, y, x), q_range = 0, q_l = 1, q_r = -1, q_o = +1, q_c = -2^num_bits + s   (z - y + x - 2^num_bits + s = 0)
+ * PRECONDITION of the meaning, which the gadget does NOT enforce: the circuit bounds x and y below 2^num_bits (range_gate or
+ * interval_gate at <= num_bits bits).  Then nothing wraps, the result is 0 or 1, and it is [x <= y] ([x < y] when strict).
+ * Without it the rows state c(z) < 2^K alone and the result is a quad without meaning (x = r - 1, y = 0 gives 1).  An item whose
+ * c(z) >= 2^K still gets all its rows; its row 0 fails.  On EXISTING Variables, their assignments read from the composer's own
+ * table; the batched form checks its arrays on the device first.  d_result_vars[i] = (the call's first new Variable) + i k; it may
+ * be NULL. */
+pg_status pg_composer_is_less_equal(pg_composer *c, pg_variable x, pg_variable y, uint64_t num_bits, int strict, pg_variable *result);
+pg_status pg_composer_is_less_equal_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_y_var,
+                                          uint64_t num_bits, int strict, uint64_t batch, pg_variable *d_result_vars);
+
 /* the composer's gate calls over device arrays of Variables, one set of selectors for the whole batch (no public
  * inputs): the loops
  *   poly_gate:             for i { composer.poly_gate(a[i], b[i], c[i], q_m, q_l, q_r, q_o, q_c, None) }

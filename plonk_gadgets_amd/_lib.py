@@ -200,6 +200,8 @@ SIGNATURES = {
     "pg_composer_interval_gate": (C.c_int, [C.c_void_p, C.c_uint64, _P(Scalar), _P(Scalar), C.c_uint64]),
     "pg_composer_interval_gate_batch": (C.c_int, [C.c_void_p, C.c_void_p, _P(Scalar), _P(Scalar), C.c_uint64, C.c_uint64]),
     "pg_composer_interval_gate_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64]),
+    "pg_composer_is_less_equal": (C.c_int, [C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, _P(C.c_uint64)]),
+    "pg_composer_is_less_equal_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint64, C.c_void_p]),
     "pg_composer_weighted_sum_ragged_batch": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint64,
                                                         C.c_void_p]),
     "pg_weighted_sum_geometry": (C.c_int, [_P(C.c_uint32), _P(C.c_uint32)]),

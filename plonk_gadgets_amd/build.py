@@ -9,7 +9,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libplonk_gadgets_hip.so")
 SOURCES = ["capi.hip"]
-HEADERS = ["experiment.hpp", "host_util.hpp", "owners.hpp", "composer_cols.hpp", "footprint.hpp", "digest.hpp", "fr.hpp", "emit.hpp", "invert.hpp", "range_gadgets.hpp", "range_gate.hpp", "interval_gate.hpp", "weighted_sum.hpp", "scalar_gadgets.hpp", "composer.hpp", "permutation.hpp", "materialize.hpp",
+HEADERS = ["experiment.hpp", "host_util.hpp", "owners.hpp", "composer_cols.hpp", "footprint.hpp", "digest.hpp", "fr.hpp", "emit.hpp", "invert.hpp", "range_gadgets.hpp", "range_gate.hpp", "interval_gate.hpp", "compare_gate.hpp", "weighted_sum.hpp", "scalar_gadgets.hpp", "composer.hpp", "permutation.hpp", "materialize.hpp",
            "permutation_product.hpp", "ntt.hpp", "quotient.hpp", "fq.hpp", "g1.hpp", "msm.hpp", "opening.hpp",
            "capi_composer.inc", "capi_dist.inc", "capi_msm.inc", "capi_open.inc",
            "fq2.hpp", "fq12.hpp", "g2.hpp", "pairing.hpp", "pairing_constants.inc", "capi_pairing.inc",

@@ -302,6 +302,28 @@ class StandardComposer:
                                                                   int(num_bits), witness_vars.shape[0]),
                  "pg_composer_interval_gate_ragged_batch")
 
+    def is_less_equal(self, x: int, y: int, num_bits: int, strict: bool = False) -> int:
+        """-> the Variable that holds [x <= y] ([x < y] when strict) PROVIDED the circuit bounds x and y below 2^num_bits (num_bits
+        even, 2..252; range_gate or interval_gate on each): the first accumulator of one range widget over num_bits + 2 bits on
+        2^num_bits + y - x - strict, ceil((num_bits / 2 + 1) / 3) + 1 rows and num_bits / 2 + 1 new Variables.  The gadget does not
+        bound its inputs; without the precondition the result has no meaning"""
+        out = C.c_uint64()
+        _chk(self._lib.pg_composer_is_less_equal(self._h, int(x), int(y), int(num_bits), int(bool(strict)), C.byref(out)),
+             "pg_composer_is_less_equal")
+        return int(out.value)
+
+    def is_less_equal_each(self, x_vars: torch.Tensor, y_vars: torch.Tensor, num_bits: int, strict: bool = False) -> torch.Tensor:
+        """for i: is_less_equal(x_vars[i], y_vars[i], num_bits, strict) -> the result Variables (device int64 arrays in and out)"""
+        assert x_vars.is_cuda and x_vars.dtype == torch.int64 and x_vars.dim() == 1 and x_vars.is_contiguous()
+        assert y_vars.is_cuda and y_vars.dtype == torch.int64 and y_vars.dim() == 1 and y_vars.is_contiguous()
+        if x_vars.shape[0] != y_vars.shape[0]:
+            raise ValueError(f"x_vars and y_vars differ in length: {x_vars.shape[0]}, {y_vars.shape[0]}")
+        res = torch.empty_like(x_vars)
+        with self._hand_over():
+            _chk(self._lib.pg_composer_is_less_equal_batch(self._h, x_vars.data_ptr(), y_vars.data_ptr(), int(num_bits), int(bool(strict)),
+                                                           x_vars.shape[0], res.data_ptr()), "pg_composer_is_less_equal_batch")
+        return res
+
     def max_bound_ragged_batch(self, max_range: torch.Tensor, witness: torch.Tensor):
         """for i: allocate(witness[i]); max_bound(max_range[i], w) -> (result Variables, num_bits per item)"""
         for x in (max_range, witness):

@@ -27,6 +27,7 @@
 #include "scalar_gadgets.hpp"
 #include "composer.hpp"
 #include "interval_gate.hpp"
+#include "compare_gate.hpp"
 #include "weighted_sum.hpp"
 #include "permutation.hpp"
 #include "materialize.hpp"
@@ -1033,6 +1034,37 @@ static pg_status interval_gate_common(pg_engine *e, const pg_variable *d_witness
         return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
     }
     using GD = pg::IntervalGateGD<false>;
+    if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+    return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
+}
+
+// the comparison gadget (compare_gate.hpp) on two arrays of existing Variables: num_bits even, 2 .. 252 (checked by the caller).
+// Every item creates Variables (z at least), so a refresh is never empty and there is no structure-only form.
+static pg_status compare_gate_common(pg_engine *e, const pg_variable *d_x_var, const pg_scalar *d_x_val, const pg_variable *d_y_var,
+                                     const pg_scalar *d_y_val, uint32_t num_bits, bool strict, uint64_t batch, uint64_t gate_base,
+                                     uint64_t var_base, uint64_t zero_var, const pg_columns *out, pg_variable *d_result_vars, void *stream,
+                                     bool values_only) {
+    using GD = pg::CompareGateGD;
+    if (!e) return fail(PG_ERR_INVALID_ARGUMENT, "engine is NULL");
+    if (batch == 0) return PG_OK;
+    PG_TRY(check_u64s(d_x_var, "d_x_var"));
+    PG_TRY(check_u64s(d_y_var, "d_y_var"));
+    PG_TRY(check_scalars(d_x_val, "x value array"));
+    PG_TRY(check_scalars(d_y_val, "y value array"));
+    PG_TRY(check_u64s(d_result_vars, "d_result_vars", true));
+    PG_TRY(check_columns(out));
+    if ((batch + GD::W - 1) / GD::W > 0xffffffffull) return fail(PG_ERR_INVALID_ARGUMENT, "batch too large for one call");
+    pg::CompareGateArgs A;
+    A.x_vars = d_x_var;
+    A.y_vars = d_y_var;
+    A.x = reinterpret_cast<const uint4 *>(d_x_val);
+    A.y = reinterpret_cast<const uint4 *>(d_y_val);
+    pg::Fr pow = pg::fr_zero();  // 2^num_bits as a canonical integer
+    pow.l[num_bits >> 6] = 1ull << (num_bits & 63);
+    A.offset = pg::fr_sub(pg::fr_to_mont(pow), strict ? pg::fr_one() : pg::fr_zero());
+    A.result_vars = d_result_vars;
+    const pg::WidgetShape shape = pg::compare_shape(num_bits);
+    A.k = shape.k; A.g = shape.g; A.pad = shape.pad;
     if (values_only) return launch_mode<GD, pg::EMIT_VALUES>(e, A, out, batch, gate_base, var_base, zero_var, stream);
     return launch_mode<GD, pg::EMIT_ALL>(e, A, out, batch, gate_base, var_base, zero_var, stream);
 }

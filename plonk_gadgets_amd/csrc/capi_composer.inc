@@ -169,7 +169,8 @@ enum class SigKind : uint64_t {
     DECOMPOSITION = 43,              // pg_scalar_decomposition_gadget
     INTERVAL_GATE_BATCH = 61,        // pg_composer_interval_gate_batch, pg_composer_interval_gate (a batch of one)
     INTERVAL_GATE_RAGGED_BATCH = 62,  // pg_composer_interval_gate_ragged_batch
-    WEIGHTED_SUM_RAGGED_BATCH = 63    // pg_composer_weighted_sum_ragged_batch
+    WEIGHTED_SUM_RAGGED_BATCH = 63,   // pg_composer_weighted_sum_ragged_batch
+    IS_LESS_EQUAL_BATCH = 64          // pg_composer_is_less_equal_batch, pg_composer_is_less_equal (a batch of one)
 };
 // kind: which call; b0, b1: its public scalars; extra: a public integer; dg: the digest of the device arrays its rows depend on
 pg_composer::Sig gadget_sig(const pg_composer *c, SigKind kind, const pg::Fr &b0, const pg::Fr &b1, uint64_t batch, uint64_t extra,
@@ -1260,7 +1261,33 @@ pg_status interval_gate_batch(pg_composer *c, const pg_variable *d_witness_var, 
         },
         [&] { note_range_items(c, c->n, 2 * batch, shape.g); });
 }
-// the single calls of the two widgets are batches of one: the Variable goes through the composer's staging words
+// the comparison gadget on two arrays of existing Variables (compare_gate.hpp): result_vars[i] = the Variable that holds
+// [x_i <= y_i] ([x_i < y_i] when strict) PROVIDED the circuit bounds both below 2^num_bits, as the first accumulator of one range
+// widget over num_bits + 2 bits on 2^num_bits + y - x - strict.  As range_gate_batch: one preflight, assignments gathered from the
+// composer's own table, no footprint, the widget rows remembered as range items.  The rows: both Variable arrays (which is x and
+// which is y), num_bits, strict and where the call lands.
+pg_status compare_num_bits(uint64_t num_bits) { return widget_num_bits("is_less_equal", pg::kCompareGateMaxBits, num_bits); }
+pg_status is_less_equal_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_y_var, uint64_t num_bits, bool strict,
+                              uint64_t batch, pg_variable *d_result_vars) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    PG_TRY(compare_num_bits(num_bits));
+    const pg::WidgetShape shape = pg::compare_shape(num_bits);
+    pg::Fr b0 = pg::fr_zero();  // (a word of the signature, not a scalar)
+    b0.l[0] = strict ? 1 : 0;
+    return var_batch(
+        c, {{d_x_var, "d_x_var"}, {d_y_var, "d_y_var"}}, batch, (uint64_t)shape.rows() * batch, (uint64_t)shape.k * batch,
+        [&](pg_composer::Sig *dg) -> pg_status {
+            PG_TRY(check_u64s(d_result_vars, "d_result_vars", true));
+            return check_var_arrays(c, {d_x_var, d_y_var}, batch, dg);
+        },
+        [&](const pg_composer::Sig &dg) { return gadget_sig(c, SigKind::IS_LESS_EQUAL_BATCH, b0, pg::fr_zero(), batch, num_bits, dg); },
+        [&](const pg_columns *at, const pg_scalar *values, bool in_place) {
+            return compare_gate_common(c->e, d_x_var, values, d_y_var, values + batch, (uint32_t)num_bits, strict, batch, c->n, c->nvars,
+                                       c->zero_var, at, d_result_vars, c->stream, in_place);
+        },
+        [&] { note_range_items(c, c->n, batch, shape.g); });
+}
+// the single calls of the widgets are batches of one: the Variable goes through the composer's staging words
 pg_status stage_variable(pg_composer *c, pg_variable witness) {
     PG_TRY(flush(c));
     PG_TRY(check_var(c, witness));
@@ -1299,6 +1326,28 @@ pg_status pg_composer_range_gate(pg_composer *c, pg_variable witness, uint64_t n
     PG_TRY(range_num_bits(num_bits));
     PG_TRY(stage_variable(c, witness));
     return range_gate_batch(c, c->stage_words(), num_bits, 1);
+}
+
+pg_status pg_composer_is_less_equal_batch(pg_composer *c, const pg_variable *d_x_var, const pg_variable *d_y_var, uint64_t num_bits,
+                                          int strict, uint64_t batch, pg_variable *d_result_vars) {
+    return is_less_equal_batch(c, d_x_var, d_y_var, num_bits, strict != 0, batch, d_result_vars);
+}
+pg_status pg_composer_is_less_equal(pg_composer *c, pg_variable x, pg_variable y, uint64_t num_bits, int strict, pg_variable *result) {
+    if (!c) return fail(PG_ERR_INVALID_ARGUMENT, "composer is NULL");
+    if (!result) return fail(PG_ERR_INVALID_ARGUMENT, "is_less_equal: result is NULL");
+    PG_TRY(compare_num_bits(num_bits));
+    PG_TRY(flush(c));
+    PG_TRY(check_var(c, x));
+    PG_TRY(check_var(c, y));
+    PG_HIP_TRY(hipSetDevice(c->e->device));
+    pg::StageBlob b{};
+    b.w[0] = x;
+    b.w[1] = y;
+    PG_TRY(stage(c, b, 2));
+    const pg_variable first = c->nvars;  // the item's first new Variable is its result
+    PG_TRY(is_less_equal_batch(c, c->stage_words(), c->stage_words() + 1, num_bits, strict != 0, 1, nullptr));
+    *result = first;
+    return PG_OK;
 }
 
 }  // extern "C"
