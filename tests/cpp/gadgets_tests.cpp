@@ -443,6 +443,93 @@ static void batched_appends_equal_loops(Engine &e) {
     for (void *p : {(void *)d_wit, (void *)d_sel, (void *)d_res, (void *)d_res2, (void *)d_wv, (void *)d_sv}) (void)hipFree(p);
 }
 
+// The Batched:: wrappers of the widgets, the comparison, the weighted sum and the ragged ladders (include/plonk_gadgets.hpp) against
+// the C ABI they forward to: every call through the C++ mirror on one composer and through pg_composer_* on a second.  Every argument
+// of a call differs from its neighbours (x from y, min from max, coefficients from constants, num_bits from the batch), so a wrapper
+// that swaps two of them builds another circuit -- or is refused, which is counted as a failure too.
+static void wrappers_equal_the_c_abi(Engine &e) {
+    const uint64_t batch = 8, terms = 8, segments = 3;
+    std::vector<pg_scalar> wit, mins, maxs, rmin, rmax, bounds, coeff, constant;
+    for (uint64_t i = 0; i < batch; i++) {
+        wit.push_back(BlsScalar::from(3 + i).s);        // below 2^4, and inside every interval below
+        mins.push_back(BlsScalar::from(1 + i % 3).s);
+        maxs.push_back(BlsScalar::from(16 + i % 3).s);  // max - min = 15 < 2^4
+        rmin.push_back(BlsScalar::from(i).s);
+        rmax.push_back(BlsScalar::from(100 + 9 * i).s);
+        bounds.push_back(BlsScalar::from(50 + 11 * i).s);
+        coeff.push_back(BlsScalar::from(2 + i).s);
+    }
+    for (uint64_t s = 0; s < terms; s++) constant.push_back(BlsScalar::from(1000 + s).s);  // (as long as coeff: a swap stays inside both)
+    const std::vector<uint64_t> seg_off = {0, 2, 5, 8}, zeros(batch, 0);
+    pg_scalar *d_wit = to_device(wit), *d_min = to_device(mins), *d_max = to_device(maxs), *d_rmin = to_device(rmin),
+              *d_rmax = to_device(rmax), *d_bounds = to_device(bounds), *d_coeff = to_device(coeff), *d_constant = to_device(constant);
+    uint64_t *d_off = to_device(seg_off);
+    const BlsScalar lo = BlsScalar::from(2), hi = BlsScalar::from(17);
+    StandardComposer a(e, 1 << 14, 1 << 14), b(e, 1 << 14, 1 << 14);
+    std::vector<std::vector<uint64_t>> ra, rb;  // the result Variables, call by call
+    uint64_t *d_res = to_device(zeros);
+    uint32_t *d_nb = to_device(std::vector<uint32_t>(batch, 0));
+    auto results = [&](std::vector<std::vector<uint64_t>> &into, StandardComposer &c, uint64_t count) {
+        pg_throw(pg_composer_sync(c.h), "sync");
+        std::vector<uint64_t> r(count);
+        (void)hipMemcpy(r.data(), d_res, count * 8, hipMemcpyDeviceToHost);
+        into.push_back(r);
+    };
+    try {
+        for (StandardComposer *c : {&a, &b}) {
+            const bool cpp = c == &a;
+            const Variable first = Batched::allocate(*c, d_wit, batch);
+            std::vector<uint64_t> x, y;
+            for (uint64_t i = 0; i < batch; i++) { x.push_back(first.index + i); y.push_back(first.index + (i + 3) % batch); }
+            uint64_t *d_x = to_device(x), *d_y = to_device(y);
+            if (cpp) {
+                Batched::range_gate(*c, d_x, 4, batch - 2);
+                Batched::interval_gate(*c, d_x, lo.s, hi.s, 6, batch - 1);
+                Batched::interval_gate(*c, d_x, d_min, d_max, 4, batch);
+                Batched::is_less_equal(*c, d_x, d_y, 4, false, batch - 3, d_res);
+                results(ra, *c, batch - 3);
+                Batched::is_less_equal(*c, d_x, d_y, 6, true, batch, d_res);
+                results(ra, *c, batch);
+                Batched::weighted_sum(*c, d_x, d_off, d_coeff, d_constant, terms, segments, d_res);
+                results(ra, *c, segments);
+                Batched::range_check_ragged(*c, d_rmin, d_rmax, d_wit, batch, d_res, d_nb);
+                results(ra, *c, batch);
+                Batched::max_bound_ragged(*c, d_bounds, d_wit, batch, d_res, d_nb);
+                results(ra, *c, batch);
+            } else {
+                pg_throw(pg_composer_range_gate_batch(c->h, d_x, 4, batch - 2), "range_gate");
+                pg_throw(pg_composer_interval_gate_batch(c->h, d_x, &lo.s, &hi.s, 6, batch - 1), "interval_gate");
+                pg_throw(pg_composer_interval_gate_ragged_batch(c->h, d_x, d_min, d_max, 4, batch), "interval_gate (ragged)");
+                pg_throw(pg_composer_is_less_equal_batch(c->h, d_x, d_y, 4, 0, batch - 3, d_res), "is_less_equal");
+                results(rb, *c, batch - 3);
+                pg_throw(pg_composer_is_less_equal_batch(c->h, d_x, d_y, 6, 1, batch, d_res), "is_less_equal (strict)");
+                results(rb, *c, batch);
+                pg_throw(pg_composer_weighted_sum_ragged_batch(c->h, d_x, d_off, d_coeff, d_constant, terms, segments, d_res), "weighted_sum");
+                results(rb, *c, segments);
+                pg_throw(pg_composer_range_check_ragged_batch(c->h, d_rmin, d_rmax, d_wit, batch, d_res, d_nb), "range_check_ragged");
+                results(rb, *c, batch);
+                pg_throw(pg_composer_max_bound_ragged_batch(c->h, d_bounds, d_wit, batch, d_res, d_nb), "max_bound_ragged");
+                results(rb, *c, batch);
+            }
+            pg_throw(pg_composer_sync(c->h), "sync");
+            (void)hipFree(d_x);
+            (void)hipFree(d_y);
+        }
+        CHECK(a.circuit_size() == b.circuit_size() && a.num_variables() == b.num_variables() && a.circuit_size() > 3);
+        const Columns ca = download(a), cb = download(b);
+        CHECK(same_structure(ca, cb));
+        CHECK(ca.vars.size() == cb.vars.size() && std::memcmp(ca.vars.data(), cb.vars.data(), ca.vars.size() * 32) == 0);
+        CHECK(a.check() == -1 && b.check() == -1);
+        CHECK(ra == rb && ra.size() == 5);
+    } catch (const std::exception &ex) {
+        std::printf("  a call was refused: %s\n", ex.what());
+        CHECK(false);
+    }
+    for (void *p : {(void *)d_wit, (void *)d_min, (void *)d_max, (void *)d_rmin, (void *)d_rmax, (void *)d_bounds, (void *)d_coeff,
+                    (void *)d_constant, (void *)d_off, (void *)d_res, (void *)d_nb})
+        (void)hipFree(p);
+}
+
 // BlsScalar::invert as the gadgets use it (src/scalar.rs:73,121): x * x^-1 == 1, zero has none
 static void scalar_invert() {
     BlsScalar inv;
@@ -485,6 +572,7 @@ int main() {
         {"scalar_invert", [&] { scalar_invert(); }},
         {"batched_appends_equal_loops", [&] { batched_appends_equal_loops(e); }},
         {"single_calls_are_queued", [&] { single_calls_are_queued(e); }},
+        {"wrappers_equal_the_c_abi", [&] { wrappers_equal_the_c_abi(e); }},
         {"scalar_decomposition_test", [&] { scalar_decomposition_test(e); }},
         {"max_bound_test", [&] { max_bound_test(e); }},
         {"range_check_test", [&] { range_check_test(e); }},

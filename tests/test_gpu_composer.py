@@ -1100,20 +1100,23 @@ def test_materialize_rows_of_batched_calls(engine):
     assert torch.equal(m["w_4_value"], cols.var_values[w4])
 
 
-@pytest.mark.parametrize("lead", [0, 1, 5])
+@pytest.mark.parametrize("lead", [0, 1, 2, 3, 5, 15])
 @pytest.mark.parametrize("kind,extra", [("max_bound", 1), ("max_bound", 2), ("range_check", 1), ("range_check", 0),
-                                        ("max_bound_allocated", 1), ("range_check_allocated", 1), ("decomposition", 1), ("decomposition", 2)])
+                                        ("max_bound_allocated", 1), ("range_check_allocated", 1), ("decomposition", 1), ("decomposition", 2),
+                                        ("range_gate", 1), ("interval_gate", 1), ("is_less_equal", 1), ("weighted_sum", 1)])
 def test_materialize_short_items_and_a_short_last_group(engine, kind, extra, lead):
     """the windowed kernel writes whole lines: a group's range of rows is cut at multiples of 16 rows, so the first rows of the next
     group come along with it (csrc/materialize.hpp: their values through the loader wave's side table).  The corner: items SHORTER
     than 16 rows (several come along, over more than one item) and a LAST group of fewer rows than that, at the very end of the
     circuit -- nothing past the circuit's last row may be touched (outputs 64 rows longer, sentinel-filled), whatever the first
-    row's alignment (`lead` single rows before the call)."""
+    row's and the first Variable's alignment (`lead` inputs and `lead` single rows before the call).  The widgets, is_less_equal and the
+    weighted sum take the windowed route that reads the wires back (MAT_READ_WIRES), which cuts at multiples of 16 rows as well."""
     import ctypes as C
     from plonk_gadgets_amd import _lib
     dev = pg.StandardComposer(engine, 1 << 15, 1 << 21)
     for _ in range(lead):
         dev.add_input(S(7))
+        dev.boolean_gate(dev.zero_var)
     bound = S(3) if kind.startswith("max_bound") else S(2)
 
     def append(comp, w):
@@ -1129,6 +1132,15 @@ def test_materialize_short_items_and_a_short_last_group(engine, kind, extra, lea
             return comp.max_bound_allocated_batch(bound, vars_, w)
         if kind == "range_check_allocated":
             return comp.range_check_allocated_batch(S(0), bound, vars_, w)
+        if kind == "range_gate":            # 4 bits: 2 rows and 1 Variable an item (the witnesses are below 2)
+            return comp.range_gate_batch(vars_, 4)
+        if kind == "interval_gate":         # 2 bits: 4 rows and 2 Variables
+            return comp.interval_gate_batch(vars_, S(0), S(3), 2)
+        if kind == "is_less_equal":         # 2 bits: 2 rows and 2 Variables
+            return comp.is_less_equal_each(vars_, vars_.flip(0), 2)
+        if kind == "weighted_sum":          # segments of 2 terms: 1 row and 1 Variable
+            return comp.weighted_sum_ragged_batch(torch.stack([vars_, vars_.flip(0)], dim=1).reshape(-1).contiguous(),
+                                                  torch.arange(0, 2 * w.shape[0] + 1, 2, dtype=torch.int64, device="cuda:0"))
         return comp.scalar_decomposition_batch(2, vars_, w)
 
     probe = pg.StandardComposer(engine, 1024, 1024)

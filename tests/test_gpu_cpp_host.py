@@ -29,5 +29,5 @@ def test_cpp_reference_suite_on_gpu():
     assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-2000:]
     for name in ("counting_scalar_bits", "scalar_decomposition_test", "max_bound_test", "range_check_test", "test_maybe_equal",
                  "test_conditionally_select_0", "test_conditionally_select_1", "test_is_not_zero", "single_calls_are_queued",
-                 "batched_appends_equal_loops"):
+                 "batched_appends_equal_loops", "wrappers_equal_the_c_abi"):
         assert f"test {name} ... ok" in p.stdout

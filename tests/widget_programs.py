@@ -152,6 +152,102 @@ class Both:
         self.ora.L.composer_constrain_to_constant(self.ora.c, int(var), F(constant), None)
         self._logged("constrain_to_constant", 1, None, n0)
 
+    # -- the other appends of the alignment sweep (tests/alignment_programs.py) -------------------------------------------------
+    def _allocated(self, var):
+        return po.AllocatedScalar(int(var), self.ora.L.composer_value(self.ora.c, int(var)))
+
+    def _own_values(self, vars_):
+        """the assignments of existing Variables, as the device array a call on allocated witnesses wants"""
+        return self.t([self.value(v) for v in vars_])
+
+    def boolean_gate(self, var):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.boolean_gate(int(var))
+        self.ora.L.composer_boolean_gate(self.ora.c, int(var))
+        self._logged("boolean_gate", 1, None, n0)
+
+    def range_check(self, mn, mx, value):
+        """allocate + range_check, the reference's single calls (recorded by the command queue)"""
+        n0 = self.ora.n
+        o = int(self.ora.L.range_check(self.ora.c, F(mn), F(mx), self.ora.allocate(po.limbs(F(value)))))
+        if self.dev is not None:
+            import plonk_gadgets_amd as pg
+            assert pg.range_check(self.dev, self.S(mn), self.S(mx), pg.AllocatedScalar.allocate(self.dev, self.S(value))) == o
+        self._logged("range_check", 1, None, n0)
+        return o
+
+    def max_bound(self, mx, value):
+        n0 = self.ora.n
+        o = int(self.ora.L.max_bound(self.ora.c, F(mx), self.ora.allocate(po.limbs(F(value))), None))
+        if self.dev is not None:
+            import plonk_gadgets_amd as pg
+            assert pg.max_bound(self.dev, self.S(mx), pg.AllocatedScalar.allocate(self.dev, self.S(value)))[0] == o
+        self._logged("max_bound", 1, None, n0)
+        return o
+
+    def max_bound_batch(self, mx, values):
+        n0 = self.ora.n
+        r = self.dev.max_bound_batch(self.S(mx), self.t(values))[0] if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.max_bound(self.ora.c, F(mx), self.ora.allocate(po.limbs(F(v))), None) for v in values])
+        self._logged("max_bound_batch", len(values), None, n0)
+        return o
+
+    def range_check_allocated_batch(self, mn, mx, vars_):
+        n0 = self.ora.n
+        r = self.dev.range_check_allocated_batch(self.S(mn), self.S(mx), self.tv(vars_), self._own_values(vars_)) \
+            if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.range_check(self.ora.c, F(mn), F(mx), self._allocated(v)) for v in vars_])
+        self._logged("range_check_allocated_batch", len(vars_), None, n0)
+        return o
+
+    def max_bound_allocated_batch(self, mx, vars_):
+        n0 = self.ora.n
+        r = self.dev.max_bound_allocated_batch(self.S(mx), self.tv(vars_), self._own_values(vars_))[0] if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.max_bound(self.ora.c, F(mx), self._allocated(v), None) for v in vars_])
+        self._logged("max_bound_allocated_batch", len(vars_), None, n0)
+        return o
+
+    def scalar_decomposition_batch(self, num_bits, vars_):
+        n0 = self.ora.n
+        r = self.dev.scalar_decomposition_batch(num_bits, self.tv(vars_), self._own_values(vars_)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.scalar_decomposition_gadget(self.ora.c, num_bits, self._allocated(v), None) for v in vars_])
+        self._logged("scalar_decomposition_batch", len(vars_), num_bits, n0)
+        return o
+
+    def conditionally_select_one_batch(self, ys, selectors):
+        n0 = self.ora.n
+        r = self.dev.conditionally_select_one_batch(self.tv(ys), self.tv(selectors)) if self.dev is not None else None
+        o = self._same_vars(r, [self.ora.L.conditionally_select_one(self.ora.c, a, b) for a, b in zip(ys, selectors)])
+        self._logged("conditionally_select_one_batch", len(ys), None, n0)
+        return o
+
+    def is_non_zero_batch(self, vars_):
+        """-> the error count; an item whose value is 0 stops at its error"""
+        n0 = self.ora.n
+        oe = [int(self.ora.L.is_non_zero(self.ora.c, int(v), self.ora.L.composer_value(self.ora.c, int(v)))) for v in vars_]
+        if self.dev is not None:
+            err, nerr = self.dev.is_non_zero_batch(self.tv(vars_))
+            assert err.cpu().numpy().tolist() == oe and nerr == sum(oe)
+        self._logged("is_non_zero_batch", len(vars_), None, n0)
+        return sum(oe)
+
+    def boolean_gate_batch(self, vars_):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.boolean_gate_batch(self.tv(vars_))
+        for v in vars_:
+            self.ora.L.composer_boolean_gate(self.ora.c, int(v))
+        self._logged("boolean_gate_batch", len(vars_), None, n0)
+
+    def constrain_to_constant_batch(self, vars_, constant):
+        n0 = self.ora.n
+        if self.dev is not None:
+            self.dev.constrain_to_constant_batch(self.tv(vars_), self.S(constant))
+        for v in vars_:
+            self.ora.L.composer_constrain_to_constant(self.ora.c, int(v), F(constant), None)
+        self._logged("constrain_to_constant_batch", len(vars_), None, n0)
+
     # -- the widgets ------------------------------------------------------------------------------------------------------------
     def range_gate(self, w, num_bits):
         n0 = self.ora.n
